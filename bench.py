@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: pileup columns / second through the consensus network forward pass.
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]        (N > 1: launched by torch.distributed.run)
 
 Metric and workload are BASELINE.json's: configs[1] = r1041_e82_400bps_sup-architecture
 consensus (GRUModel 10 -> 2 x bi-GRU(128) -> Linear(5) -> softmax, reference
@@ -11,7 +11,12 @@ is already resident in HBM; `value` = all columns processed by all ranks / max-o
 time of K steps.  Multi-GPU = independent replicas on disjoint window shards, no collective on
 the data path (weak scaling: per-GPU batch fixed).
 
-Also reported on the same JSON line:
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, and the roofline of the
+dominant kernel from the hipEvents of those same steps).  `--dump-outputs DIR` also writes what the last timed step
+handed its caller, DIR/probs.npy (float32; a fixed, seeded sample of windows if it exceeds 64 MB), from inputs that are
+the same in every run with the same arguments.
+
+With `--full`, also reported on the same JSON line:
   host_to_host  (= metric_8d) the rate SURVEY.md section 8d defines: host tensor in -> host tensor out through
                 `model.predict_on_batch` (reference models.py:303-313): median of >= 5 timed batches after
                 0.6 s of untimed ones (the first six are on the line as they came: `first_calls_ms`)
@@ -48,11 +53,16 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: host-to-host, fed loop, PCIe diet, CPU baseline and "
+                         "parity, sequential scan, the half-precision and rl_lstm384 lines (off: setup, warm-up, the timed steps, the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, <= 64 MB in all)")
     ap.add_argument("--batch", type=int, default=200, help="windows per step per GPU")
     ap.add_argument("--chunk-len", type=int, default=10000, help="pileup columns per window")
     ap.add_argument("--depth", type=int, default=50)
     ap.add_argument("--overlap", type=int, default=1, help="layer-1 projection GEMM under the tail of the layer-0 recurrence (0 off, 1 on)")
-    ap.add_argument("--cpu-budget", type=float, default=60.0, help="wall-clock cap of the CPU baseline in seconds (0 = skip)")
+    ap.add_argument("--cpu-budget", type=float, default=60.0, help="--full: wall-clock cap of the CPU baseline in seconds (0 = skip)")
     ap.add_argument("--variant", type=int, default=None, help="MDK_VARIANT_* override (1 = exact fp32 kernels)")
     ap.add_argument("--tile", type=int, default=0, help="recurrence windows per work-group (0 auto, 4, 8, 16 = half precision only)")
     ap.add_argument("--half", action="store_true", help="model.half() path (reference GPU default)")
@@ -60,7 +70,7 @@ def parse():
                     help="path of a .npy with reference probabilities (n, T, 5) of the first n windows of this run's batch: `parity` is "
                          "then this run's host-to-host result against it (how the fp32 line hands its CPU result to its --half child)")
     ap.add_argument("--extra-half", type=int, default=1,
-                    help="1 (default): the fp32-parity line also carries `extra.half`, the same batch with model.half() -- what the "
+                    help="--full, 1 (default): the fp32-parity line also carries `extra.half`, the same batch with model.half() -- what the "
                          "reference CLI selects on a GPU unless --full_precision (prediction.py:164-168); 0 = skip")
     ap.add_argument("--deferred-store", type=int, default=None, help="recurrence: store h_t from inside step t+1")
     ap.add_argument("--scan-split", type=int, default=None,
@@ -86,16 +96,16 @@ def parse():
     ap.add_argument("--pageable-input", action="store_true",
                     help="host-to-host batches only from a pageable input tensor (the reference's collate) instead of the page-locked "
                          "one the engine's Batch.collate produces")
-    ap.add_argument("--host-reps", type=int, default=7, help="timed host-to-host batches (median reported)")
+    ap.add_argument("--host-reps", type=int, default=7, help="--full: timed host-to-host batches (median reported)")
     ap.add_argument("--extra-rl", type=float, default=15.0,
-                    help="seconds of CPU baseline granted to the rl_lstm384 line that the default run appends under `extra` (0 = no extra line)")
+                    help="seconds of CPU baseline granted to the rl_lstm384 line that a --full run appends under `extra` (0 = no extra line)")
     ap.add_argument("--margin-256", type=int, default=0,
-                    help="1: also time 3 steps at a margin of 256 columns (`value_at_margin_256`: what a model with a longer memory runs at); "
+                    help="1 (with --full): also time 3 steps at a margin of 256 columns (`value_at_margin_256`: what a model with a longer memory runs at); "
                          "off by default -- the larger workspace it allocates hands the old one back to the driver")
     ap.add_argument("--full-out", default=os.path.join(ROOT, "bench_full.json"),
                     help="where the complete record goes (stdout carries only the compact line the driver parses)")
     ap.add_argument("--loop-batches", type=int, default=32,
-                    help="batches of the fed loop (threaded loader -> collate -> predict_on_batch -> writer; 0 = skip)")
+                    help="--full: batches of the fed loop (threaded loader -> collate -> predict_on_batch -> writer; 0 = skip)")
     return ap.parse_args()
 
 
@@ -550,6 +560,8 @@ def main_rl(args, print_line=True):
         t = eng.timing()
         front.append(t["front_ms"]); total.append(t["total_ms"])
     elapsed, _ = dist.timed_steps(ranks, step, lambda: torch.cuda.synchronize(dev), steps=args.steps, warmup=args.warmup)
+    if args.dump_outputs and print_line and ranks.rank == 0:
+        dump_outputs(args.dump_outputs, {"probs": holder["y"]})
     front, total = front[-args.steps:], total[-args.steps:]
     cols = B * P
     value = ranks.world * cols * args.steps / elapsed
@@ -582,21 +594,22 @@ def main_rl(args, print_line=True):
                      "kernels": rl_kernel_entries(wide, B, P, D, statistics.mean(front), statistics.mean(total), args.half, achieved),
                      "wide_retries": eng.timing()["wide_retries"]},
     }
-    # host tensor in -> host tensor out, as the prediction loop calls it
-    from medaka_amd.torch_ext import Batch
-    xb = Batch(read_level_features=x.cpu())
-    h2h = []
-    for _ in range(4):
-        t0 = time.perf_counter()
-        m.predict_on_batch(xb)
-        h2h.append(time.perf_counter() - t0)
-    h_med = ranks.max_over_ranks(statistics.median(h2h[1:]))
-    result["host_to_host"] = {"value": ranks.world * cols / h_med, "unit": "pileup columns/s", "ms_per_batch_median": 1e3 * h_med,
-                              "timed_batches": 3, "frac_of_device_resident": (cols / h_med) / (value / ranks.world),
-                              "what": f"model.predict_on_batch(Batch(read_level_features=<uint8 CPU tensor, {x.numel() / 1e6:.0f} MB>)) -> CPU tensor"}
-    result["metric_8d"] = {"value": result["host_to_host"]["value"], "unit": "pileup columns/s", "what": "SURVEY.md 8d: host tensor in -> host tensor out"}
+    if args.full:
+        # host tensor in -> host tensor out, as the prediction loop calls it
+        from medaka_amd.torch_ext import Batch
+        xb = Batch(read_level_features=x.cpu())
+        h2h = []
+        for _ in range(4):
+            t0 = time.perf_counter()
+            m.predict_on_batch(xb)
+            h2h.append(time.perf_counter() - t0)
+        h_med = ranks.max_over_ranks(statistics.median(h2h[1:]))
+        result["host_to_host"] = {"value": ranks.world * cols / h_med, "unit": "pileup columns/s", "ms_per_batch_median": 1e3 * h_med,
+                                  "timed_batches": 3, "frac_of_device_resident": (cols / h_med) / (value / ranks.world),
+                                  "what": f"model.predict_on_batch(Batch(read_level_features=<uint8 CPU tensor, {x.numel() / 1e6:.0f} MB>)) -> CPU tensor"}
+        result["metric_8d"] = {"value": result["host_to_host"]["value"], "unit": "pileup columns/s", "what": "SURVEY.md 8d: host tensor in -> host tensor out"}
     if ranks.rank == 0:
-        if args.cpu_budget > 0 and ranks.world == 1:
+        if args.full and args.cpu_budget > 0 and ranks.world == 1:
             # CPU baseline: the functional PyTorch-CPU restatement of LatentSpaceLSTM.forward (oracle/rl_oracle.py, pinned
             # to the unmodified reference) on a bounded sample: 8 windows x 2000 positions x D reads, 1 warm-up + median of 3
             from oracle import rl_oracle
@@ -625,7 +638,7 @@ def main_rl(args, print_line=True):
                                 "columns_checked": int(xs.shape[0] * xs.shape[1])}
         if print_line:
             result["summary"] = {"unit": "M columns/s (ms)", "value": round(value / 1e6, 3), "ms_per_step": round(result["ms_per_step"], 2),
-                                 "metric_8d": round(result["host_to_host"]["value"] / 1e6, 3),
+                                 "metric_8d": round(result["host_to_host"]["value"] / 1e6, 3) if "host_to_host" in result else None,
                                  "parity_max_abs_dp": (result.get("parity") or {}).get("max_abs_dp"),
                                  "cpu_baseline": (result.get("cpu_baseline") or {}).get("value")}
             emit(result, args.full_out)
@@ -735,6 +748,34 @@ def emit(result, full_out):
     print(compact_line(result), flush=True)
 
 
+DUMP_BUDGET = 60_000_000    # bytes of all `--dump-outputs` arrays together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """`--dump-outputs`: the arrays the timed path handed its caller in its last step, as DIR/<name>.npy in float32 (float64
+    stays float64), so that two builds can be compared output for output.  Over DUMP_BUDGET bytes in all, every array keeps
+    the same fixed, seeded sample of rows along its first (window) axis, in order."""
+    import numpy as np
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in host.items():
+        if total > DUMP_BUDGET:
+            if a.ndim < 2 or a.nbytes // a.shape[0] * len(host) > DUMP_BUDGET:
+                a = a.reshape(-1)                  # (rows too large to sample: sample elements)
+            keep = max(1, a.shape[0] * DUMP_BUDGET // total)
+            rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], size=keep, replace=False))
+            a = np.ascontiguousarray(a[rows])
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": bool(total > DUMP_BUDGET)}
+    log(f"outputs written to {out_dir}: {written}")
+    return written
+
+
 def settle_margin(eng, step, max_calls=72):
     """Untimed calls until the split scan's margin learner (include/medaka_amd.h "scan_split_adapt") has stopped moving, so that
     the timed region measures the DEFAULT configuration in its steady state -- learner on, no trial left to run: a smaller
@@ -765,7 +806,7 @@ def half_section(args, ref_probs):
     import tempfile
     import numpy as np
     with tempfile.TemporaryDirectory() as tmp:
-        cmd = [sys.executable, os.path.abspath(__file__), "--half", "--cpu-budget", "0", "--extra-rl", "0", "--extra-half", "0",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--half", "--cpu-budget", "0", "--extra-rl", "0", "--extra-half", "0",
                "--steps", str(max(5, args.steps)), "--warmup", str(max(2, args.warmup)), "--batch", str(args.batch),
                "--chunk-len", str(args.chunk_len), "--depth", str(args.depth), "--loop-batches", str(args.loop_batches)]
         if ref_probs is not None:
@@ -917,6 +958,8 @@ def main():
     elapsed, mine = dist.timed_steps(ranks, step_timed, lambda: torch.cuda.synchronize(dev),
                                      steps=args.steps, warmup=args.warmup)
     log(f'timed region done: {elapsed:.3f}s for {args.steps} steps')
+    if args.dump_outputs and ranks.rank == 0:
+        dump_outputs(args.dump_outputs, {"probs": out_holder["y"]})
     # keep only the timed steps' kernel records
     n_layers = len(eng.timing()["rec_ms"])
     rec_ms = rec_ms[-args.steps * n_layers:]
@@ -938,53 +981,54 @@ def main():
                               "head_ms_per_step": statistics.mean(head_ms[-args.steps:])}), flush=True)
         ranks.close()
         return
-    # host tensor in -> host tensor out (what run_prediction's loop sees), every rank at once
-    eng.enable_timing(False)
-    from medaka_amd.torch_ext import Batch
-    x_cpu = torch.from_numpy(x_host)
-    # the input tensor as the engine's Batch.collate builds it (page-locked; medaka_amd.torch_ext.stack_counts, installed over
-    # the reference's collate by integration.install) -- and, for comparison, as the reference's torch.stack leaves it (pageable)
-    variants = [("pageable (reference collate)", x_cpu)] if args.pageable_input else \
-               [("page-locked (engine collate)", x_cpu.pin_memory()), ("pageable (reference collate)", x_cpu)]
-    if args.stream_host is not None:
-        eng.set_option("stream_host", args.stream_host)
-    # The first calls are recorded as they come (`first_calls_ms`), untimed calls follow until `settle_s` seconds of host-path
-    # traffic have passed (at least 8 calls), and the median is taken over the timed calls after those.  Why: device memory
-    # handed back to the driver (hipFree) is wiped by the kernel on the DMA engines, in the background, at ~25 GB/s -- and while
-    # that runs every strided copy of the host path takes 130 us longer (10.9 instead of 8.0 ms per call).  Until round 5 every
-    # audit of the split scan freed 12 GB of gi workspace, so the ~40 calls behind each were slow ("the box's DMA needs 0.3 s to
-    # wake up", profiles/r4_experiments/README.md); the audit allocates nothing now (profiles/r5_experiments/README.md section 9)
-    # and the first calls are at the settled rate unless something else in the process has just freed device memory.
-    h2h_all, first_calls = {}, {}
-    settle_s, settle = 0.6, 0
-    for vname, xv in variants:
-        xb = Batch(counts_matrix=xv)
-        h2h = []
+    if args.full:
+        # host tensor in -> host tensor out (what run_prediction's loop sees), every rank at once
+        eng.enable_timing(False)
+        from medaka_amd.torch_ext import Batch
+        x_cpu = torch.from_numpy(x_host)
+        # the input tensor as the engine's Batch.collate builds it (page-locked; medaka_amd.torch_ext.stack_counts, installed over
+        # the reference's collate by integration.install) -- and, for comparison, as the reference's torch.stack leaves it (pageable)
+        variants = [("pageable (reference collate)", x_cpu)] if args.pageable_input else \
+                   [("page-locked (engine collate)", x_cpu.pin_memory()), ("pageable (reference collate)", x_cpu)]
+        if args.stream_host is not None:
+            eng.set_option("stream_host", args.stream_host)
+        # The first calls are recorded as they come (`first_calls_ms`), untimed calls follow until `settle_s` seconds of host-path
+        # traffic have passed (at least 8 calls), and the median is taken over the timed calls after those.  Why: device memory
+        # handed back to the driver (hipFree) is wiped by the kernel on the DMA engines, in the background, at ~25 GB/s -- and while
+        # that runs every strided copy of the host path takes 130 us longer (10.9 instead of 8.0 ms per call).  Until round 5 every
+        # audit of the split scan freed 12 GB of gi workspace, so the ~40 calls behind each were slow ("the box's DMA needs 0.3 s to
+        # wake up", profiles/r4_experiments/README.md); the audit allocates nothing now (profiles/r5_experiments/README.md section 9)
+        # and the first calls are at the settled rate unless something else in the process has just freed device memory.
+        h2h_all, first_calls = {}, {}
+        settle_s, settle = 0.6, 0
+        for vname, xv in variants:
+            xb = Batch(counts_matrix=xv)
+            h2h = []
 
-        def host_step():
+            def host_step():
+                t0 = time.perf_counter()
+                out_holder["p"] = model.predict_on_batch(xb)
+                h2h.append(time.perf_counter() - t0)
+            log(f'host-to-host batches, input {vname}')
+            n_timed = max(5, args.host_reps)
+            t_settle = time.perf_counter()
+            while len(h2h) < 8 or ranks.max_over_ranks(time.perf_counter() - t_settle) < settle_s:      # (every rank leaves the loop together)
+                host_step()
+            settle = max(settle, len(h2h))
+            dist.timed_steps(ranks, host_step, lambda: None, steps=n_timed, warmup=2)
+            h2h_all[vname] = (ranks.max_over_ranks(statistics.median(h2h[-n_timed:])), n_timed)
+            first_calls[vname] = [round(1e3 * t, 3) for t in h2h[:6]]
+            log(f'host-to-host, input {vname}: median {1e3 * h2h_all[vname][0]:.2f} ms (first calls: ' + " ".join(f"{1e3 * t:.1f}" for t in h2h[:6]) + ')')
+        primary = variants[0][0]
+        h_med, n_h2h = h2h_all[primary]
+        xb = Batch(counts_matrix=variants[0][1])
+        eng.set_option("stream_host", 0)
+        plain = []
+        for _ in range(4):
             t0 = time.perf_counter()
-            out_holder["p"] = model.predict_on_batch(xb)
-            h2h.append(time.perf_counter() - t0)
-        log(f'host-to-host batches, input {vname}')
-        n_timed = max(5, args.host_reps)
-        t_settle = time.perf_counter()
-        while len(h2h) < 8 or ranks.max_over_ranks(time.perf_counter() - t_settle) < settle_s:      # (every rank leaves the loop together)
-            host_step()
-        settle = max(settle, len(h2h))
-        dist.timed_steps(ranks, host_step, lambda: None, steps=n_timed, warmup=2)
-        h2h_all[vname] = (ranks.max_over_ranks(statistics.median(h2h[-n_timed:])), n_timed)
-        first_calls[vname] = [round(1e3 * t, 3) for t in h2h[:6]]
-        log(f'host-to-host, input {vname}: median {1e3 * h2h_all[vname][0]:.2f} ms (first calls: ' + " ".join(f"{1e3 * t:.1f}" for t in h2h[:6]) + ')')
-    primary = variants[0][0]
-    h_med, n_h2h = h2h_all[primary]
-    xb = Batch(counts_matrix=variants[0][1])
-    eng.set_option("stream_host", 0)
-    plain = []
-    for _ in range(4):
-        t0 = time.perf_counter()
-        model.predict_on_batch(xb)
-        plain.append(time.perf_counter() - t0)
-    eng.set_option("stream_host", 1)
+            model.predict_on_batch(xb)
+            plain.append(time.perf_counter() - t0)
+        eng.set_option("stream_host", 1)
 
     result = {
         "metric": "pileup columns/sec (consensus bi-GRU inference)",
@@ -1011,7 +1055,10 @@ def main():
                            "option \"scan_split_adapt\" left at its default: the timed steps are the default configuration)"
                            if split["chunks"] > 1 else "sequential scan",
                            margins_seen=margins_seen),
-        "host_to_host": {
+    }
+    result["value_basis"] = "device-resident (inputs in HBM at the start of the timed region); SURVEY 8d's host-to-host rate is `metric_8d` (--full)"
+    if args.full:
+        result["host_to_host"] = {
             "value": ranks.world * cols_per_step / h_med, "unit": "pileup columns/s",
             "ms_per_batch_median": 1e3 * h_med, "timed_batches": n_h2h, "warmup": 2 + settle, "settle_seconds": settle_s,
             "first_calls_ms": first_calls[primary],
@@ -1028,19 +1075,17 @@ def main():
                     "profiles/r5_experiments/README.md section 9); the fed loop below hands every "
                     "NEW batch to the device from the Batcher thread, so there the input does not wait for PCIe",
             "one_copy_each_way_ms_per_batch": 1e3 * statistics.median(plain),
-        },
-    }
-    result["metric_8d"] = {"value": result["host_to_host"]["value"], "unit": "pileup columns/s",
-                           "ms_per_batch_median": result["host_to_host"]["ms_per_batch_median"],
-                           "what": "SURVEY.md section 8d's metric: columns / wall time of predict_on_batch calls, host tensor in -> host tensor out "
-                                   "(= host_to_host.value).  `value` above is the device-resident rate: this build's task statement fixes `value` as "
-                                   "\"whole-job throughput with inputs already resident in HBM when the timed region starts\" and rules the "
-                                   "PCIe-inclusive rate out of it; neither BASELINE.json nor SURVEY.md says that, SURVEY 8d asks for THIS figure"}
-    result["value_basis"] = "device-resident (inputs in HBM at the start of the timed region); SURVEY 8d's host-to-host rate is `metric_8d`"
+        }
+        result["metric_8d"] = {"value": result["host_to_host"]["value"], "unit": "pileup columns/s",
+                               "ms_per_batch_median": result["host_to_host"]["ms_per_batch_median"],
+                               "what": "SURVEY.md section 8d's metric: columns / wall time of predict_on_batch calls, host tensor in -> host tensor out "
+                                       "(= host_to_host.value).  `value` above is the device-resident rate: this build's task statement fixes `value` as "
+                                       "\"whole-job throughput with inputs already resident in HBM when the timed region starts\" and rules the "
+                                       "PCIe-inclusive rate out of it; neither BASELINE.json nor SURVEY.md says that, SURVEY 8d asks for THIS figure"}
 
     shared_loop = None
     ref_probs = None
-    if args.shared_gpu and ranks.world > 1 and args.loop_batches > 2:
+    if args.full and args.shared_gpu and ranks.world > 1 and args.loop_batches > 2:
         # K processes per GPU, each running the whole fed loop (loader threads -> engine collate -> predict_on_batch ->
         # writer): the deployment `medaka_amd.launch --procs-per-gpu K` produces; aggregate = sum over the processes
         from medaka_amd import torch_ext
@@ -1106,13 +1151,13 @@ def main():
             "kernel_ms_per_step": {"rec": sum(rec_ms) / args.steps, "gi": statistics.mean(gi_ms[-n:]),
                                    "head": statistics.mean(head_ms[-n:]), "device_total": statistics.mean(total_ms[-n:])},
         }
-        if args.cpu_budget > 0 and ranks.world == 1:   # the CPU baseline is a single-GPU-run figure
+        if args.full and args.cpu_budget > 0 and ranks.world == 1:   # the CPU baseline is a single-GPU-run figure
             probs = out_holder["p"].numpy()
             result["cpu_baseline"], result["parity"], ref_probs = cpu_baseline(
                 os.path.join(ROOT, "tests", "golden", "weights_trained.npz"), x_host, probs, args.cpu_budget)
             if result["cpu_baseline"]["value"]:
                 result["speedup_vs_cpu_baseline"] = value / result["cpu_baseline"]["value"]
-        if args.parity_ref:
+        if args.full and args.parity_ref:
             ref = np.load(args.parity_ref)
             got = out_holder["p"].numpy()[:ref.shape[0]]
             result["parity"] = {"max_abs_dp": float(np.abs(got - ref).max()),
@@ -1120,24 +1165,25 @@ def main():
                                 "argmax_identical": bool((got.argmax(-1) == ref.argmax(-1)).all()),
                                 "columns_checked": int(ref.shape[0] * T), "tolerance": 1e-4,
                                 "against": "the reference probabilities handed in with --parity-ref (the fp32 line's PyTorch-CPU result)"}
-        if args.loop_batches > 2 and ranks.world == 1:
+        if args.full and args.loop_batches > 2 and ranks.world == 1:
             result["fed_loop"] = loop_report(model, B, T, args.depth, 4321, args.loop_batches,
                                              result["host_to_host"]["value"])
-        # the same with the PCIe diet (SURVEY 8f f2 + f3): uint16 counts + uint32 depth in (24 B/column),
-        # argmax class + its probability out (5 B/column)
-        cnt = np.minimum(np.rint(x_host * 60.0), 65535).astype(np.uint16)
-        dep = np.full(x_host.shape[:2], 60, dtype=np.uint32)
-        diet = []
-        for _ in range(8):       # (the first calls allocate the aux buffers and the page-locked results)
-            t0 = time.perf_counter()
-            out_holder["diet"] = model.predict_on_counts(cnt, dep, decoded=True)
-            diet.append(time.perf_counter() - t0)
-        result["pcie_diet_columns_per_s"] = cols_per_step / statistics.median(diet[3:])
+        if args.full:
+            # the same with the PCIe diet (SURVEY 8f f2 + f3): uint16 counts + uint32 depth in (24 B/column),
+            # argmax class + its probability out (5 B/column)
+            cnt = np.minimum(np.rint(x_host * 60.0), 65535).astype(np.uint16)
+            dep = np.full(x_host.shape[:2], 60, dtype=np.uint32)
+            diet = []
+            for _ in range(8):       # (the first calls allocate the aux buffers and the page-locked results)
+                t0 = time.perf_counter()
+                out_holder["diet"] = model.predict_on_counts(cnt, dep, decoded=True)
+                diet.append(time.perf_counter() - t0)
+            result["pcie_diet_columns_per_s"] = cols_per_step / statistics.median(diet[3:])
     # Sections that re-arm the margin learner (setting "scan_split" does) or make the workspace grow (a larger margin: the old
     # activations are handed back to the driver, which wipes them on the DMA engines -- behind which the host path's strided
     # copies wait) come LAST: in round 5 they sat in front of the host-path sections, and the half line's
     # first hundred host-to-host calls ran at 8.6 ms instead of 5.6.
-    if split["chunks"] > 1:
+    if args.full and split["chunks"] > 1:
         # the same steps as the plain sequential scan, for the record (not `value`): 3 steps after 1 warm-up
         eng.set_option("scan_split", 0)
         seq_elapsed, _ = dist.timed_steps(ranks, step, lambda: torch.cuda.synchronize(dev), steps=3, warmup=1)
@@ -1165,17 +1211,18 @@ def main():
             result["value_at_margin_256"] = {"value": ranks.world * cols_per_step * 3 / m_elapsed, "unit": "pileup columns/s",
                                              "ms_per_step": 1e3 * m_elapsed / 3, "steps": 3, "chunks": m_split["chunks"],
                                              "columns": m_split["columns"], "status": m_split["status"]}
-    if ranks.world == 1 and not args.shared_gpu and not args.half and args.extra_half:
+    if args.full and ranks.world == 1 and not args.shared_gpu and not args.half and args.extra_half:
         # the precision `medaka inference` selects on a GPU by default, on the same line (reference prediction.py:164-168)
         try:
             result.setdefault("extra", {})["half"] = half_section(args, ref_probs)
         except Exception as exc:                      # the headline line must not depend on it
             result.setdefault("extra", {})["half"] = {"error": f"{type(exc).__name__}: {exc}"}
-    if ranks.world == 1 and not args.shared_gpu and args.extra_rl > 0:
+    if args.full and ranks.world == 1 and not args.shared_gpu and args.extra_rl > 0:
         # BASELINE config 4b on the same line: the read-level rl_lstm384 architecture, timed by this same run
         import copy
         a2 = copy.copy(args)
         a2.model, a2.steps, a2.warmup, a2.cpu_budget, a2.half = "rl384", 3, 1, (min(args.cpu_budget, args.extra_rl) if args.cpu_budget > 0 else 0), False
+        a2.dump_outputs = None                        # (the outputs written are the headline's)
         del model, eng
         torch.cuda.empty_cache()
         try:

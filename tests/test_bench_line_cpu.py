@@ -87,3 +87,24 @@ def test_kernel_table_takes_its_work_group_shape_from_the_engine(half, B, chunks
             assert e["frac_issued_of_fp16_peak"] >= e["frac_algorithmic_of_fp16_peak"], e
     if half and chunks == 5:
         assert plan["windows_per_group"] == 8 and plan["work_groups"] == 125     # (rocprof: grid 64000 x 2 threads = 125 x 2 work-groups)
+
+
+def test_dump_outputs_writes_float32_and_samples_over_the_budget(tmp_path):
+    """`--dump-outputs`: float32 (float64 kept) as DIR/<name>.npy; over the budget, the same seeded rows on every call, all
+    arrays together under it."""
+    import numpy as np
+    bench = _bench()
+    small = np.arange(2 * 3 * 5, dtype=np.float16).reshape(2, 3, 5)
+    bench.dump_outputs(str(tmp_path / "a"), {"probs": small, "f64": np.ones(4)})
+    got = np.load(tmp_path / "a" / "probs.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.astype(np.float32))
+    assert np.load(tmp_path / "a" / "f64.npy").dtype == np.float64
+    rows = bench.DUMP_BUDGET // (1000 * 5 * 4) * 2                 # twice what fits
+    big = np.random.default_rng(1).random((rows, 1000, 5), dtype=np.float32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"probs": big})
+    b, c = np.load(tmp_path / "b" / "probs.npy"), np.load(tmp_path / "c" / "probs.npy")
+    assert np.array_equal(b, c) and b.shape[1:] == big.shape[1:] and 0 < b.shape[0] < rows
+    assert os.path.getsize(tmp_path / "b" / "probs.npy") <= 64_000_000
+    idx = [int(np.flatnonzero(big[:, 0, 0] == r[0, 0])[0]) for r in b]      # rows of the original, in order
+    assert idx == sorted(set(idx)) and np.array_equal(big[idx], b)

@@ -264,7 +264,7 @@ def test_two_rank_bench_on_one_gpu(tmp_path):
     from conftest import ROOT
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("MDK_SCAN_SPLIT", None)
-    common = ["--steps", "3", "--warmup", "1", "--cpu-budget", "0", "--loop-batches", "0", "--host-reps", "3", "--extra-rl", "0"]
+    common = ["--full", "--steps", "3", "--warmup", "1", "--cpu-budget", "0", "--loop-batches", "0", "--host-reps", "3", "--extra-rl", "0"]
     # (stdout carries the compact driver line only; everything else the run measured is in the side file)
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--shared-gpu", "--full-out", str(tmp_path / "one.json")] + common,
                          capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
@@ -290,6 +290,48 @@ def test_two_rank_bench_on_one_gpu(tmp_path):
     assert 0.6 <= ratio <= 1.6, ratio
     assert r2["host_to_host"]["value"] > 0 and r2["roofline"]["kernels"]
     assert r2["barrier_backend"] == "gloo" and r2["ranks_seen"] == 2
+
+
+def test_plain_bench_run_and_its_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`, the run every change is measured with: one line with the
+    headline keys, exactly K timed steps, nothing of `--full` measured, at most 30 s outside the steps; DIR/probs.npy is what the
+    last step computed from the seeded synthetic batch -- the same bits in a second run, and the CPU oracle's probabilities."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    from medaka_amd import synth
+    from oracle import oracle
+    env = dict(os.environ)
+    env.pop("MDK_SCAN_SPLIT", None)
+    B, T, steps, warmup = 16, 4000, 3, 2
+    runs = []
+    for k in ("a", "b"):
+        t0 = time.perf_counter()
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                            "--batch", str(B), "--chunk-len", str(T), "--full-out", str(tmp_path / f"{k}.json"),
+                            "--dump-outputs", str(tmp_path / k)], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+        wall = time.perf_counter() - t0
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        line = json.loads(lines[0])
+        full = json.load(open(tmp_path / f"{k}.json"))
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert line[key] is not None, key
+        assert line["steps"] == steps and line["warmup"] == warmup and line["higher_is_better"] is True
+        assert abs(line["value"] - B * T / (1e-3 * line["ms_per_step"])) <= 1e-6 * line["value"]
+        assert not set(full) & {"host_to_host", "fed_loop", "cpu_baseline", "parity", "sequential_scan", "extra"}, sorted(full)
+        outside = wall - (steps + warmup) * 1e-3 * line["ms_per_step"]
+        print(f"plain run {k}: {line['ms_per_step']:.3f} ms per step, {outside:.1f} s outside the steps")
+        assert outside <= 30.0, outside
+        runs.append(np.load(tmp_path / k / "probs.npy"))
+    a, b = runs
+    assert a.dtype == np.float32 and a.shape == (B, T, 5)
+    assert np.array_equal(a, b)
+    x = synth.counts_windows(B, T, depth=50, seed=1234)            # bench.py's batch (B <= 40: one tile)
+    ref = oracle.c_gru_forward(x[:2], dict(np.load(os.path.join(GOLD, "weights_trained.npz"))))
+    assert float(np.abs(a[:2] - ref).max()) <= 1e-4
 
 
 def test_rccl_that_cannot_work_falls_back_on_hardware():

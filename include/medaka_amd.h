@@ -165,6 +165,27 @@ int mdk_gru_drop_pending(mdk_gru *m);
 int mdk_gru_forward_dev(mdk_gru *m, const float *x_dev, int B, int T, float *probs_dev,
                         void *stream);
 
+/* Stream-ordered device forward: same contraction and contract as mdk_gru_forward_dev, but it never waits on the host
+ * (except: timing enabled; more than "async_depth" calls in flight -- the new call then waits for the oldest one, the only
+ * wait of the steady state; first call at a shape that grows the workspace).  The split certificate, the fp32 probe of half
+ * mode and the audit are decided on the device, in stream order.  A rejected call's probs_dev holds the sequential scan's
+ * result.  mdk_gru_get_split reports the last call and waits for it.  Successive calls may use different streams: each call's
+ * stream waits, on the device, for the previous call (the model's workspace is shared).
+ * What differs from mdk_gru_forward_dev, by design:
+ *   - a rejected call delivers the sequential scan, not a retry at the next margin; the larger margin (or the back-off) applies
+ *     from the next call ENQUEUED after the rejection has been retired (by a later call, mdk_gru_get_split, mdk_gru_drop_pending);
+ *   - the audit cadence ("scan_split_audit_every") counts split calls enqueued, not calls certified, and the back-off counts
+ *     calls enqueued;
+ *   - half precision: a call whose margin has a probe in flight from an earlier call is gated on that probe's verdict instead
+ *     of running its own.
+ * Every other entry of this model first waits for the stream-ordered calls in flight (mdk_gru_drop_pending retires only those
+ * already done).  Not for graph capture.
+ * Memory: the split is planned with gi (the exact-projection fallback's input, 3 KB per virtual column) and the gated repair with
+ * the sequential plan's own buffers, all allocated on the first call at a shape and kept: about 13 GB more than a certified
+ * mdk_gru_forward_dev call at 200 x 10 000 (6.9 GB of gi for the 1000 x 2256 virtual batch, 6.1 GB for the repair's side-stream
+ * projection), the same buffers a rejected synchronous call allocates. */
+int mdk_gru_forward_dev_async(mdk_gru *m, const float *x_dev, int B, int T, float *probs_dev, void *stream);
+
 /* Replaces `TorchModel.half()` (models.py:298-301): MDK_PREC_FP32 (default) / MDK_PREC_FP16. */
 int mdk_gru_set_precision(mdk_gru *m, int precision);
 int mdk_gru_set_variant(mdk_gru *m, int variant);
@@ -253,6 +274,9 @@ int mdk_gru_set_normalise(mdk_gru *m, int normalise);
  *                                                   as one copy behind the forward otherwise
  *   "max_rows_per_pass"    = 0 (16 Mi) | n          column budget (B*T) of one pass over the workspace;
  *                                                   larger batches run as equal passes
+ *   "async_depth"          = 8 | 1..64              mdk_gru_forward_dev_async: the most calls whose records are not yet retired;
+ *                                                   at the limit a new call waits for the oldest one (the entry's only host
+ *                                                   wait in the steady state)
  * (the debug library adds "ablate": see the MDK_DEBUG_HOOKS block at the end of this header) */
 int mdk_gru_set_option(mdk_gru *m, const char *key, int value);
 

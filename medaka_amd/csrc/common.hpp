@@ -26,6 +26,13 @@ __device__ __forceinline__ floatx4 mfma16(half8 a, half8 b, floatx4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 
+// Gate of a predicated pass (the stream-ordered entry, gru_split.hpp): null = run, else the kernel returns at once when the
+// word is non-zero.  A kernel earlier in stream order wrote it, so the whole grid reads the same value; every kernel that takes
+// one tests it first thing, before any barrier or LDS traffic, so no work-group can wait on one that has left.
+__device__ __forceinline__ bool gated_off(const int *gate) {
+    return gate != nullptr && __builtin_amdgcn_readfirstlane(*gate) != 0;
+}
+
 // exp2/rcp based logistic and tanh: ~2 ulp, error << 1e-6 absolute on (0,1)/(-1,1)
 __device__ __forceinline__ float fast_exp(float x) {
     return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f);

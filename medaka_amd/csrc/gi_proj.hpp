@@ -30,8 +30,9 @@ __global__ __launch_bounds__(768) void k_gi_small(
     const float *__restrict__ bias,   // [D][384]     folded bias
     float *__restrict__ gi,           // gi_t
     int B, int T, int K, int n_tiles, int t_per_block, const float *__restrict__ out_scale_p,
-    const int *__restrict__ cond, int want)
+    const int *__restrict__ cond, int want, const int *__restrict__ gate)
 {
+    if (gated_off(gate)) return;                                     // predicated pass (common.hpp)
     if (cond != nullptr && ((*cond != 0) != (want != 0))) return;   // see k_pack_x
     const int tile = blockIdx.x;
     const int d = blockIdx.y;
@@ -108,8 +109,10 @@ __global__ __launch_bounds__(512, MT <= 4 ? 4 : 2) void k_gi_gemm(
     const float *__restrict__ out_scale_p, float a_scale,   // a_scale: power-of-two operand scale of act_in
     int strip0,                                              // first 8-step strip of this launch
     const int *__restrict__ cond, int want,                  // run only if (*cond != 0) == want (cond may be null)
-    int t_end)                                               // columns >= t_end are neither read nor written
+    int t_end,                                               // columns >= t_end are neither read nor written
+    const int *__restrict__ gate = nullptr)                  // predicated pass (common.hpp gated_off)
 {
+    if (gated_off(gate)) return;
     if (cond != nullptr && ((*cond != 0) != (want != 0))) return;
     constexpr int DIN = KSTEPS / 4;            // directions of the input activations
     constexpr int NP = DIN * 128;              // 8-float pieces per activation block

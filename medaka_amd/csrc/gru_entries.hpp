@@ -90,8 +90,8 @@ static void release_slot(mdk_gru *m, mdk_gru::StageSlot *sl) {
 }
 
 // nothing of a batch started ahead may survive: wait for it, free its slot (its token is spent: the caller's ordinary host
-// entry answers).  Every entry but the pipelined one starts with this.
-static void drop_pending(mdk_gru *m) {
+// entry answers).
+static void drop_early(mdk_gru *m) {
     if (!m->pending.st.valid) return;
     m->pending.st.valid = false;
     m->early_dropped++;
@@ -102,11 +102,42 @@ static void drop_pending(mdk_gru *m) {
     m->pending.slot = nullptr;
 }
 
+// Every entry but the pipelined one and the stream-ordered one starts with this: the batch started ahead is dropped, and the calls of
+// the stream-ordered entry still in flight are waited for and retired (they share the workspace, on streams of the caller's)
+static void drop_pending(mdk_gru *m) {
+    if (m->async_count) (void)retire_async(m, true);
+    drop_early(m);
+}
+
 extern "C" int mdk_gru_drop_pending(mdk_gru *m) {
     if (!m) return fail(MDK_ERR_ARG, "null model");
     HIP_TRY(hipSetDevice(m->device));
-    drop_pending(m);
-    return MDK_OK;
+    int rc = retire_async(m, false);         // (stream-ordered calls: only those already done)
+    drop_early(m);
+    return rc;
+}
+
+// ---- the stream-ordered device forward (gru_split.hpp enqueue_async) ----------------------------------------
+extern "C" int mdk_gru_forward_dev_async(mdk_gru *m, const float *x_dev, int B, int T, float *probs_dev, void *stream) {
+    if (!m) return fail(MDK_ERR_ARG, "null model");
+    if (B < 0 || T < 0) return fail(MDK_ERR_ARG, "negative shape B=%d T=%d", B, T);
+    HIP_TRY(hipSetDevice(m->device));
+    drop_early(m);                           // (before the early return below: a batch started ahead never survives an entry)
+    if (B == 0 || T == 0) { memset(&m->last, 0, sizeof(m->last)); m->last.n_layers = m->desc.num_layers; return MDK_OK; }
+    if (!x_dev || !probs_dev) return fail(MDK_ERR_ARG, "null buffer");
+    int rc = ensure_async(m);
+    if (!rc) rc = retire_async(m, false);
+    // the ring is full: the oldest call is waited for -- the only wait of the steady state
+    if (!rc && m->async_count == m->async_slots.size()) {
+        const size_t i = m->async_head;
+        if (hipEventSynchronize(m->async_slots[i].done) != hipSuccess) return fail(MDK_ERR_DEVICE, "hipEventSynchronize failed");
+        rc = retire_async(m, false);
+    }
+    if (rc) return rc;
+    // NULL = the legacy default stream, as for any HIP call
+    rc = enqueue_async(m, x_dev, B, T, probs_dev, (hipStream_t)stream);
+    if (rc) (void)hipDeviceSynchronize();    // (a half-enqueued call: nothing of it may still run when the caller sees the error)
+    return rc;
 }
 
 // enqueue the forward of the batch staged right after `token` (same shape), if it is there, into the other context
@@ -152,6 +183,7 @@ extern "C" int mdk_gru_forward_pipelined(mdk_gru *m, unsigned long long token, i
     if (!m) return fail(MDK_ERR_ARG, "null model");
     if (!probs_host || token == 0) return fail(MDK_ERR_ARG, "null buffer / token");
     HIP_TRY(hipSetDevice(m->device));
+    if (m->async_count) { int rc0 = retire_async(m, true); if (rc0) return rc0; }     // (stream-ordered calls in flight share the workspace)
     const auto t_entry = std::chrono::steady_clock::now();
     mdk_gru::StageSlot *sl = nullptr;
     mdk_gru::Started pre;

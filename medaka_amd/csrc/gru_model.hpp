@@ -190,6 +190,28 @@ struct mdk_gru : Ctx {
     int opt_early_start = 1;                 // 0: the staged entry never starts the next batch's forward ahead of its call
     int opt_stage_overlap = 2;               // a batch started ahead: its layer 0 beside the previous batch's layer 1 (0 off, 1 half precision, 2 both)
     long early_started = 0, early_used = 0, early_dropped = 0;
+    // the stream-ordered entry (mdk_gru_forward_dev_async, gru_split.hpp): the split's certificate, the half-precision probe and the
+    // audit are decided on the device (AsyncWords); what the host learns from a call is fed to it later, from a page-locked record
+    struct AsyncSlot {
+        hipEvent_t done = nullptr;           // behind the call's last work (the copy of its record)
+        bool split = false;                  // ran as a split scan (else: the sequential passes, nothing to learn)
+        int S = 1, G = 0, Tv = 0, T = 0, precision = 0;
+        int status = MDK_SPLIT_NOT_USED;     // a call that did not split: what mdk_gru_get_split reports for it
+        bool probe_ran = false;              // this call ran the fp32-parity probe of its margin
+        bool audited = false;                // this call enqueued an audit (it ran if the split was certified)
+        int audit_key = 0;
+        long epoch = 0;                      // learner_epoch when the call was enqueued
+    };
+    int opt_async_depth = 8;                 // calls whose records are not yet retired; at the limit the next call waits for the oldest
+    AsyncWords *async_dev = nullptr;         // device: gates, the last probe's verdict, the record of the call in progress
+    unsigned *probe_flag = nullptr;          // device: certificate words of the fp32-parity probe
+    AsyncRecord *async_host = nullptr;       // page-locked ring of records, one per slot
+    std::vector<AsyncSlot> async_slots;
+    size_t async_head = 0, async_count = 0;  // oldest slot not yet retired, slots in flight
+    hipEvent_t async_last = nullptr;         // behind the last call: the next one's stream waits for it (the workspace is shared)
+    int probe_inflight_G = 0;                // margin of the probe whose verdict sits in async_dev and is not yet retired (0: none)
+    int audit_inflight_key = 0;              // audit key of an audit enqueued and not yet retired
+    long learner_epoch = 0;                  // bumped by every retirement that moves the margin learner or the back-off (retire_one)
 };
 
 
@@ -242,6 +264,8 @@ static void free_ctx(Ctx &c) {
 }
 
 static void drop_pending(mdk_gru *m);
+static void free_async(mdk_gru *m);
+static int retire_async(mdk_gru *m, bool wait);
 
 extern "C" void mdk_gru_destroy(mdk_gru *m) {
     if (!m) return;
@@ -274,6 +298,7 @@ extern "C" void mdk_gru_destroy(mdk_gru *m) {
     if (m->shares_copy_streams) { free_ctx(static_cast<Ctx &>(*m)); free_ctx(m->other); }
     else { free_ctx(m->other); free_ctx(static_cast<Ctx &>(*m)); }
     free_dev(m->aux_dev); free_dev(m->x_dev); free_dev(m->audit);
+    free_async(m);
     if (m->stage_stream) { (void)hipStreamSynchronize(m->stage_stream); (void)hipStreamDestroy(m->stage_stream); }
     for (auto &sl : m->stage) { free_dev(sl.dev); if (sl.ready) (void)hipEventDestroy(sl.ready); }
     delete m;
@@ -561,6 +586,9 @@ extern "C" int mdk_gru_set_option(mdk_gru *m, const char *key, int value) {
         m->margin.quiet = 0;
     } else if (!strcmp(key, "scan_split_probe")) {
         m->opt_split_probe = value ? 1 : 0;
+    } else if (!strcmp(key, "async_depth")) {
+        if (value < 1 || value > 64) return fail(MDK_ERR_ARG, "async_depth must be 1..64");
+        m->opt_async_depth = value;              // (drop_pending above has retired every call in flight: the ring is resized by the next call)
     } else if (!strcmp(key, "scan_split_margin")) {
         if (value < 16 || value > 4096 || value % 8) return fail(MDK_ERR_ARG, "scan_split_margin must be a multiple of 8 in 16..4096");
         m->opt_split_margin = value;
@@ -594,6 +622,11 @@ extern "C" int mdk_gru_get_timing(mdk_gru *m, mdk_gru_timing *out) {
 }
 extern "C" int mdk_gru_get_split(mdk_gru *m, mdk_gru_split *out) {
     if (!m || !out) return fail(MDK_ERR_ARG, "null argument");
+    if (m->async_count) {                    // stream-ordered calls in flight: the last one is what is reported -- wait for them
+        HIP_TRY(hipSetDevice(m->device));
+        int rc = retire_async(m, true);
+        if (rc) return rc;
+    }
     *out = m->last_split;
     return MDK_OK;
 }

@@ -217,6 +217,8 @@ struct Pass {
     const SplitPlan *sp;
     std::vector<hipEvent_t> *join_later;     // split call: the events behind its last result copies (run_split waits for them
                                              // after its certificate kernel) instead of a wait on `s`
+    const int *gate;                         // predicated pass (the stream-ordered entry's repair and audit): every kernel of the
+                                             // pass returns at once while *gate != 0 (common.hpp gated_off); null = always runs
     struct OutRange { hipEvent_t ready; int t0, nt; int launch; };
     std::vector<OutRange> out_ranges;        // column ranges to copy out; issued after every launch is enqueued, because a
                                              // copy into pageable memory may block the calling thread until it is done
@@ -258,7 +260,7 @@ void Pass::launch_gemm(const LayerDev &Lg, const float *src, float *gi_out, hipS
 #define MDK_GEMM(KS, HPF)                                                                          \
     hipLaunchKernelGGL((k_gi_gemm<KS, HPF>), grid, dim3(512), (size_t)2 * kGemmMT * KS * 64 * sizeof(half8), st, \
                        src, Lg.wih_frag, Lg.bias_gi, gi_out, n_tiles, T, D, Lg.inv_scale_gi, Lg.up_scale_rec, kActScale, strip0, \
-                       gcond, gwant, t_end)
+                       gcond, gwant, t_end, gate)
     if (D == 2) { if (P.hp) MDK_GEMM(8, true); else MDK_GEMM(8, false); }
     else { if (P.hp) MDK_GEMM(4, true); else MDK_GEMM(4, false); }
 #undef MDK_GEMM
@@ -272,29 +274,29 @@ void Pass::launch_head(const float *src, hipStream_t st, int t0, int nt) {
         const long n = (long)n_tiles * nt * kTileWin;
         const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 256 * 8);
         if (sp) hipLaunchKernelGGL(k_head_combine<true>, dim3(blocks), dim3(256), 0, st, (const float *)m->lpart, m->lin_b, probs, nb, T,
-                                   n_tiles, D, m->desc.normalise, t0, nt, *sp);
+                                   n_tiles, D, m->desc.normalise, t0, nt, *sp, gate);
         else hipLaunchKernelGGL(k_head_combine<false>, dim3(blocks), dim3(256), 0, st, (const float *)m->lpart, m->lin_b, probs, nb, T,
-                                n_tiles, D, m->desc.normalise, t0, nt, SplitPlan{});
+                                n_tiles, D, m->desc.normalise, t0, nt, SplitPlan{}, gate);
         return;
     }
     const long n_blocks = (long)n_tiles * nt;
     const long blocks = std::min<long>((n_blocks + 3) / 4, 256 * 8);
     if (sp)       // (plan_split: bidirectional models only)
         hipLaunchKernelGGL((k_head_tiled<2, true>), dim3((unsigned)blocks), dim3(256), 0, st, src, m->lin_w, m->lin_b,
-                           probs, nb, T, n_tiles, m->desc.normalise, t0, nt, *sp);
+                           probs, nb, T, n_tiles, m->desc.normalise, t0, nt, *sp, gate);
     else if (D == 2)
         hipLaunchKernelGGL(k_head_tiled<2>, dim3((unsigned)blocks), dim3(256), 0, st, src, m->lin_w, m->lin_b,
-                           probs, nb, T, n_tiles, m->desc.normalise, t0, nt, SplitPlan{});
+                           probs, nb, T, n_tiles, m->desc.normalise, t0, nt, SplitPlan{}, gate);
     else
         hipLaunchKernelGGL(k_head_tiled<1>, dim3((unsigned)blocks), dim3(256), 0, st, src, m->lin_w, m->lin_b,
-                           probs, nb, T, n_tiles, m->desc.normalise, t0, nt, SplitPlan{});
+                           probs, nb, T, n_tiles, m->desc.normalise, t0, nt, SplitPlan{}, gate);
 }
 
 void Pass::pack_cols(const LayerDev &Lp, const float *src, int t0, int nt, hipStream_t st) {
     if (nt <= 0) return;
     const size_t need = (size_t)P.n_wg * nt * kXfragLanes;
     hipLaunchKernelGGL(k_pack_x, dim3((unsigned)((need + 255) / 256)), dim3(256), 0, st, src, m->xfrag, P.nb, P.T,
-                       Lp.K, P.nq, P.hp ? 1 : 0, P.n_wg, Lp.x_scale, m->oor_flag, t0, nt, sp ? *sp : SplitPlan{});
+                       Lp.K, P.nq, P.hp ? 1 : 0, P.n_wg, Lp.x_scale, m->oor_flag, t0, nt, sp ? *sp : SplitPlan{}, gate);
 }
 
 // host -> device copy of the columns [t0, t0 + nt) of every window of this pass
@@ -319,17 +321,17 @@ void Pass::launch_gi_small(int l, const LayerDev &Ld, const int *cond) {
         const int vec = (F % 2 == 0 && reinterpret_cast<uintptr_t>(in) % 8 == 0) ? 2 : 1;
         const size_t n = (size_t)P.nb * T * F / vec;
         hipLaunchKernelGGL(k_split_gather, dim3((unsigned)std::min<size_t>((n + 255) / 256, 256 * 16)), dim3(256), 0, s,
-                           in, m->xv, *sp, F, vec, 0, T, cond);
+                           in, m->xv, *sp, F, vec, 0, T, cond, gate);
         src = m->xv;
     }
     hipLaunchKernelGGL(k_gi_small<16>, dim3(P.n_tiles, P.D, (T + tpb - 1) / tpb), dim3(768), 0, s, src,
-                       Ld.w_ih_t, Ld.bias_gi, m->gi, P.nb, T, Ld.K, P.n_tiles, tpb, Ld.up_scale_rec, cond, 1);
+                       Ld.w_ih_t, Ld.bias_gi, m->gi, P.nb, T, Ld.K, P.n_tiles, tpb, Ld.up_scale_rec, cond, 1, gate);
 }
 
 #define MDK_LAUNCH_REC_T(NQV, XIN, HPF, A, DSV, CND, WANT)                                         \
     hipLaunchKernelGGL((k_rec_mfma<MDK_PF, NQV, XIN, HPF, 0, A, DSV>), rgrid(), dim3(512), 0, s, gi_src, m->xfrag, \
                        Ld.wx_frag, Ld.whh_frag, Ld.b_hn, outp, P.n_tiles, P.T, P.D, Ld.inv_scale_rec,    \
-                       reverse_mask(), CND, WANT, rs0, rns)
+                       reverse_mask(), CND, WANT, rs0, rns, gate)
 // deferred HBM store of h_t (default) or the store behind the gate math; ablation builds use the latter
 #define MDK_LAUNCH_REC(NQV, XIN, HPF, A, CND, WANT)                                                \
     do { if ((A) == 0 && m->opt_deferred_store) MDK_LAUNCH_REC_T(NQV, XIN, HPF, 0, true, CND, WANT); \
@@ -346,7 +348,7 @@ void Pass::launch_rec(int l, const LayerDev &Ld, const float *gi_src, float *out
     hipLaunchKernelGGL((k_rec_fused<KS, HD, HPF>), rgrid(), dim3(512), fused_lds_bytes(KS, HPF), s, in, Ld.wih_frag, Ld.bias_gi, \
                        Ld.whh_frag, Ld.b_hn, outp, P.n_tiles, P.T, D, Ld.inv_scale_rec, Ld.inv_scale_gi, Ld.up_scale_rec,   \
                        kActScale, reverse_mask(), rs0, rns, (const half8 *)m->wlin_frag, m->lin_inv_scale, m->lpart,        \
-                       (const float *)m->lin_b, probs, P.nb, (int)m->desc.normalise, sp ? *sp : SplitPlan{})
+                       (const float *)m->lin_b, probs, P.nb, (int)m->desc.normalise, sp ? *sp : SplitPlan{}, gate)
 #define MDK_LAUNCH_FUSED_P(KS, HD) do { if (P.hp) MDK_LAUNCH_FUSED(KS, HD, true); else MDK_LAUNCH_FUSED(KS, HD, false); } while (0)
 #define MDK_LAUNCH_FUSED_H(KS) do { if (hd == 2) MDK_LAUNCH_FUSED_P(KS, 2); else if (hd == 1) MDK_LAUNCH_FUSED_P(KS, 1); else MDK_LAUNCH_FUSED_P(KS, 0); } while (0)
         if (D == 2) MDK_LAUNCH_FUSED_H(8); else MDK_LAUNCH_FUSED_H(4);
@@ -374,7 +376,7 @@ void Pass::launch_rec_fallback(const LayerDev &Ld, const float *gi_src, float *o
 #define MDK_LAUNCH_FB(NQV, HPF)                                                                    \
     hipLaunchKernelGGL((k_rec_mfma<MDK_PF - 1, NQV, false, HPF>), rgrid(), dim3(512), 0, s, gi_src, m->xfrag, \
                        Ld.wx_frag, Ld.whh_frag, Ld.b_hn, outp, P.n_tiles, P.T, P.D, Ld.inv_scale_rec,    \
-                       reverse_mask(), cnd, 1, rs0, rns)
+                       reverse_mask(), cnd, 1, rs0, rns, gate)
     const int nq = P.nq;
     if (P.hp) { if (nq == 1) MDK_LAUNCH_FB(1, true); else if (nq == 2) MDK_LAUNCH_FB(2, true); else MDK_LAUNCH_FB(4, true); }
     else { if (nq == 1) MDK_LAUNCH_FB(1, false); else MDK_LAUNCH_FB(2, false); }
@@ -432,10 +434,10 @@ int Pass::run_exact() {
     long blocks = std::min<long>((M + 15) / 16, 256 * 16);
     if (D == 2)
         hipLaunchKernelGGL(k_linear_softmax<4>, dim3((unsigned)blocks), dim3(256), 0, s, in, m->lin_w,
-                           m->lin_b, probs, M, m->desc.normalise);
+                           m->lin_b, probs, M, m->desc.normalise, gate);
     else
         hipLaunchKernelGGL(k_linear_softmax<2>, dim3((unsigned)blocks), dim3(256), 0, s, in, m->lin_w,
-                           m->lin_b, probs, M, m->desc.normalise);
+                           m->lin_b, probs, M, m->desc.normalise, gate);
     if ((rc = tm.end())) return rc;
     HIP_TRY(hipGetLastError());
     if (P.io_out) HIP_TRY(hipMemcpyAsync(io->p_host, probs, p_bytes, hipMemcpyDeviceToHost, s));
@@ -749,8 +751,9 @@ int Pass::run() {
 }
 
 static int forward_pass(mdk_gru *m, const PassPlan &P, const float *x, float *probs, hipStream_t s,
-                        EvTimer &tm, const HostIO *io, const SplitPlan *sp = nullptr, std::vector<hipEvent_t> *join_later = nullptr) {
-    Pass pass{m, P, x, probs, s, tm, io, sp, join_later};
+                        EvTimer &tm, const HostIO *io, const SplitPlan *sp = nullptr, std::vector<hipEvent_t> *join_later = nullptr,
+                        const int *gate = nullptr) {
+    Pass pass{m, P, x, probs, s, tm, io, sp, join_later, gate};
     return pass.run();
 }
 
@@ -789,9 +792,10 @@ static int finish_timing(mdk_gru *m, EvTimer &tm, hipStream_t s) {
 }
 
 // all passes of one call; x_host / probs_host (may be null) select the streamed host path per pass.  `lean`: plan for the
-// regime without gi (plan_pass); the CALLER looks at the range flag afterwards (range_flag_raised) and repeats without it
+// regime without gi (plan_pass); the CALLER looks at the range flag afterwards (range_flag_raised) and repeats without it.
+// `gate` (device-resident x and probabilities only): every kernel of the passes is predicated on it (Pass::gate)
 static int run_passes(mdk_gru *m, const float *x_dev, int B, int T, float *probs_dev, hipStream_t s,
-                      const float *x_host, float *probs_host, bool lean = false) {
+                      const float *x_host, float *probs_host, bool lean = false, const int *gate = nullptr) {
     memset(&m->last, 0, sizeof(m->last));
     m->last.n_layers = m->desc.num_layers;
     // windows per pass, bounded so that the workspace stays within a fixed column budget
@@ -805,8 +809,9 @@ static int run_passes(mdk_gru *m, const float *x_dev, int B, int T, float *probs
         per_pass = std::min(fit - fit % kTileWin, (per_pass + kTileWin - 1) / kTileWin * kTileWin);
     int rc;
     if (n_pass > 1) lean = false;                  // (the range flag is per pass: only a single pass can leave it to the caller)
-    bool need_gi = !lean;
-    if (lean) {
+    const bool host_checks = lean && !gate;        // (nobody on the host looks at a predicated pass: its range decision stays on the device)
+    bool need_gi = !host_checks;
+    if (host_checks) {
         PassPlan P;
         if ((rc = plan_pass(m, (int)std::min(per_pass, (size_t)B), T, nullptr, nullptr, P, true, true))) return rc;
         need_gi = P.need_gi;
@@ -821,8 +826,8 @@ static int run_passes(mdk_gru *m, const float *x_dev, int B, int T, float *probs
         if (probs_host) io.p_host = probs_host + b0 * T * C;
         const HostIO *iop = (x_host || probs_host) ? &io : nullptr;
         PassPlan P;                                  // (the range flag is per pass: the fallback stays on the device here)
-        if ((rc = plan_pass(m, nb, T, iop, nullptr, P, lean, lean))) return rc;
-        if ((rc = forward_pass(m, P, x_dev + b0 * T * F, probs_dev + b0 * T * C, s, tm, iop))) return rc;
+        if ((rc = plan_pass(m, nb, T, iop, nullptr, P, host_checks, lean))) return rc;
+        if ((rc = forward_pass(m, P, x_dev + b0 * T * F, probs_dev + b0 * T * C, s, tm, iop, nullptr, nullptr, gate))) return rc;
     }
     return finish_timing(m, tm, s);
 }

@@ -112,8 +112,10 @@ static bool plan_split(const mdk_gru *m, int B, int T, SplitPlan &p) {
 // A split call in two halves, so that the staged entry can enqueue the NEXT batch's forward before it waits for this one's
 // certificate: split_enqueue = every launch and copy of the call (nothing here waits for the device), split_finish = the wait,
 // the range flag, the certificate.  run_split = one after the other.
+// `dflag` (the stream-ordered entry): the certificate goes to these device words and stays there -- nothing is copied home, and the
+// range decision is the device's (gi and the fallback launches are planned in)
 static int split_enqueue(mdk_gru *m, const SplitPlan &sp, const float *x_dev, float *probs_dev, hipStream_t s,
-                         const float *x_host, float *probs_host, EvTimer &tm, bool *need_gi) {
+                         const float *x_host, float *probs_host, EvTimer &tm, bool *need_gi, unsigned *dflag = nullptr) {
     const size_t F = m->desc.num_features;
     const int Bv = sp.S * sp.B;
     const size_t cols = (size_t)Bv * sp.Tv;
@@ -131,7 +133,7 @@ static int split_enqueue(mdk_gru *m, const SplitPlan &sp, const float *x_dev, fl
     io.p_host = probs_host;
     if (probs_host && probs_host == m->tail_host) io.p_host_dev = m->tail_dev;      // (the cold host entry: the last chunks may leave by kernel)
     PassPlan P;                    // this call synchronises for its certificate anyway: it looks at the range flag itself
-    int rc = plan_pass(m, Bv, sp.Tv, probs_host ? &io : nullptr, &sp, P, /*host_checks_range=*/true);
+    int rc = plan_pass(m, Bv, sp.Tv, probs_host ? &io : nullptr, &sp, P, /*host_checks_range=*/dflag == nullptr);
     if (rc) return rc;
     *need_gi = P.need_gi;
     if ((rc = ensure_workspace(m, (((size_t)Bv + kTileWin - 1) / kTileWin * kTileWin) * (size_t)sp.Tv, P.need_gi))) return rc;
@@ -142,7 +144,8 @@ static int split_enqueue(mdk_gru *m, const SplitPlan &sp, const float *x_dev, fl
         HIP_TRY(hipEventRecord(a, s));
         m->dbg_spans.push_back({a, b});
     }
-    HIP_TRY(hipMemsetAsync(m->split_flag, 0, kSplitFlagWords * sizeof(unsigned), s));
+    unsigned *flag = dflag ? dflag : m->split_flag;
+    HIP_TRY(hipMemsetAsync(flag, 0, kSplitFlagWords * sizeof(unsigned), s));
     // Host buffers.  x crosses PCIe whole, one contiguous copy in front of the forward: all of it is needed within the
     // first half of layer 0 (1 ms of work against 1.4 ms of PCIe), so slabs gain nothing -- measured both as DMA slabs and
     // as copy kernels on the mapped buffer (profiles/r4_experiments/README.md); callers that can, hand x over early
@@ -160,8 +163,8 @@ static int split_enqueue(mdk_gru *m, const SplitPlan &sp, const float *x_dev, fl
     rc = forward_pass(m, P, x_dev, probs_dev, s, tm, probs_host ? &io : nullptr, &sp, &out_done);
     if (rc) return rc;
     hipLaunchKernelGGL(k_split_verify, dim3((unsigned)((sp.B + kVerifyWin - 1) / kVerifyWin), (unsigned)(8 * (sp.S - 1))), dim3(128), 0, s,
-                       (const float *)m->act[0], (const float *)m->act[1], sp, m->split_flag);
-    HIP_TRY(hipMemcpyAsync(m->split_host, m->split_flag, kSplitFlagWords * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+                       (const float *)m->act[0], (const float *)m->act[1], sp, flag);
+    if (!dflag) HIP_TRY(hipMemcpyAsync(m->split_host, m->split_flag, kSplitFlagWords * sizeof(unsigned), hipMemcpyDeviceToHost, s));
     // (no gi, hence no device-side fallback in this pass: the range flag goes home with the certificate)
     if (!P.need_gi) HIP_TRY(hipMemcpyAsync(m->oor_host, m->oor_flag, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipEventRecord(m->kernels_done, s));        // the call's last kernel: the other context's next forward may start behind it
@@ -484,4 +487,246 @@ static int start_call(mdk_gru *m, const float *x_dev, int B, int T, float *probs
     m->wait_before_l1 = nullptr;
     st->valid = true;
     return MDK_OK;
+}
+
+// ---- the stream-ordered device forward (mdk_gru_forward_dev_async) ---------------------------------------
+// run_forward waits for the certificate because the HOST decides what a split call delivers.  Here the device does: the split runs into
+// probs_dev, k_split_decide reduces its certificate (and the fp32-parity probe's, half precision) into gate words, the sequential
+// passes follow into probs_dev predicated on "rejected" and the audit predicated on "certified" -- each an empty launch per kernel
+// when its gate is closed.  What run_forward learns from a call (margin learner, back-off, probe and audit counters, last_split) is
+// learned when the call's record is retired: it is copied to a page-locked ring slot behind the call, and read once its event is done.
+
+// feed the host's bookkeeping from one retired call -- what run_forward does after its wait, in the same order
+static void retire_one(mdk_gru *m, const mdk_gru::AsyncSlot &sl, const AsyncRecord &r) {
+    const int fallbacks = m->last_split.fallbacks;
+    memset(&m->last_split, 0, sizeof(m->last_split));
+    m->last_split.chunks = 1; m->last_split.columns = sl.T; m->last_split.fallbacks = fallbacks;
+    m->last_split.status = sl.status;
+    if (!sl.split) { report_audits(m); return; }
+    m->last_split.chunks = sl.S; m->last_split.margin = sl.G; m->last_split.columns = sl.Tv;
+    m->last_split.max_delta = r.worst;
+    if (sl.probe_ran) {
+        m->probes_done++;
+        m->probe_last_delta = r.probe_delta;
+        m->probed_ok.erase(std::remove(m->probed_ok.begin(), m->probed_ok.end(), sl.G), m->probed_ok.end());
+        if (r.probe_ok) m->probed_ok.push_back(sl.G);
+        if (m->probe_inflight_G == sl.G) m->probe_inflight_G = 0;
+        if (!r.probe_ok) m->last_split.max_delta = r.probe_delta;      // (as run_forward: a rejected probe is the call's certificate)
+    }
+    if (sl.audited && m->audit_inflight_key == sl.audit_key) m->audit_inflight_key = 0;
+    // Calls enqueued before an earlier one's verdict was retired were planned under a learner state that verdict has since changed
+    // (a margin, a trial, the back-off): only a call of the current EPOCH -- enqueued after the last retirement that moved the learner
+    // or the back-off -- moves them.  So one episode of rejections moves the learner one step and starts ONE back-off, as in
+    // run_forward, however many calls were in flight (at the largest margin GIVE_UP leaves the margin where it was: without the epoch
+    // every call in flight would double the back-off again).
+    const bool current = sl.epoch == m->learner_epoch && sl.precision == m->precision &&
+                         (m->margin.cur ? m->margin.cur : m->opt_split_margin) == sl.G;
+    if (r.certified) {
+        m->last_split.status = MDK_SPLIT_CERTIFIED;
+        if (current) {
+            m->split_backoff = 0;
+            const int cur0 = m->margin.cur, trial0 = m->margin.trial_back;
+            const float quiet_thr = 0.25f * (sl.precision == MDK_PREC_FP16 ? kSplitEpsHalf : kSplitEps);
+            const int was = m->margin.certified(sl.G, r.worst, quiet_thr, m->opt_scan_split == 1 ? m->opt_split_adapt : 0);
+            if (was) fprintf(stderr, "[medaka_amd] split scan: certified at a margin of %d columns (was %d): kept\n", sl.G, was);
+            if (m->margin.cur != cur0 || m->margin.trial_back != trial0) m->learner_epoch++;
+        }
+        if (sl.audited) {
+            float dp;
+            memcpy(&dp, &r.audit_bits, sizeof(float));
+            m->audits_done++;
+            m->audit_worst = std::max(m->audit_worst, dp);
+            m->last_split.audited = 1;
+            m->last_split.audit_max_dp = dp;
+            if (dp <= (sl.precision == MDK_PREC_FP16 ? kAuditTolHalf : kAuditTol)) {
+                m->split_audited_key = sl.audit_key;
+            } else {
+                fprintf(stderr, "[medaka_amd] split scan: an audit found |p_split - p_sequential| = %.3g behind a certified split (margin %d): "
+                                "the sequential result was delivered and the split scan is off for this model\n", dp, sl.G);
+                m->audit_failures++;
+                m->last_split.status = MDK_SPLIT_REJECTED;
+                m->last_split.fallbacks++;
+                m->split_disabled = true;
+                m->learner_epoch++;
+            }
+        }
+        report_audits(m);
+        return;
+    }
+    // rejected: the sequential scan was delivered.  The learner takes one step; the next call ENQUEUED after this point uses it.
+    m->last_split.status = MDK_SPLIT_REJECTED;
+    m->last_split.fallbacks++;
+    report_audits(m);
+    if (!current) return;
+    m->margin.quiet = 0;
+    if (m->opt_scan_split != 1) return;
+    int was_trial = 0;
+    const MarginLearner::Next nx = m->margin.rejected(sl.G, &was_trial);
+    m->learner_epoch++;
+    if (was_trial) {
+        fprintf(stderr, "[medaka_amd] split scan: a margin of %d columns does not certify (junction states differ by %.3g): back to %d\n",
+                sl.G, m->last_split.max_delta, m->margin.cur);
+    } else if (nx == MarginLearner::GIVE_UP) {
+        m->split_disabled = true;
+        m->split_backoff = m->split_backoff ? std::min<long>(2 * m->split_backoff, 4096) : 64;
+        m->split_retry_in = m->split_backoff;
+        if (m->split_backoff == 64)
+            fprintf(stderr, "[medaka_amd] split scan: junction states still differ by %.3g at a margin of %d columns: sequential scans "
+                            "for the next %ld calls, then another try (back-off doubling up to 4096 calls)\n",
+                    m->last_split.max_delta, sl.G, m->split_backoff);
+    } else {
+        fprintf(stderr, "[medaka_amd] split scan: junction states differed by %.3g at a margin of %d columns: margin %d from now on\n",
+                m->last_split.max_delta, sl.G, m->margin.cur);
+    }
+}
+
+// retire the calls in flight, oldest first: those whose event is complete (`wait` = false: hipEventQuery, never blocks), or all of them
+static int retire_async(mdk_gru *m, bool wait) {
+    while (m->async_count) {
+        const size_t i = m->async_head;
+        const hipError_t e = wait ? hipEventSynchronize(m->async_slots[i].done) : hipEventQuery(m->async_slots[i].done);
+        if (e == hipErrorNotReady) { (void)hipGetLastError(); break; }
+        if (e != hipSuccess) return fail(MDK_ERR_DEVICE, "hipEventQuery failed: %s", hipGetErrorString(e));
+        retire_one(m, m->async_slots[i], m->async_host[i]);
+        m->async_head = (i + 1) % m->async_slots.size();
+        m->async_count--;
+    }
+    return MDK_OK;
+}
+
+static void free_async(mdk_gru *m) {
+    (void)retire_async(m, true);
+    for (auto &sl : m->async_slots) if (sl.done) (void)hipEventDestroy(sl.done);
+    m->async_slots.clear();
+    m->async_head = m->async_count = 0;
+    m->async_last = nullptr;
+    if (m->async_host) (void)hipHostFree(m->async_host);
+    m->async_host = nullptr;
+    free_dev(reinterpret_cast<float *>(m->async_dev)); m->async_dev = nullptr;
+    free_dev(reinterpret_cast<float *>(m->probe_flag)); m->probe_flag = nullptr;
+    m->probe_inflight_G = m->audit_inflight_key = 0;
+}
+
+// the device words and a ring of "async_depth" slots (a new depth: every call in flight is retired first -- a wait, once)
+static int ensure_async(mdk_gru *m) {
+    if (!m->async_dev) {
+        HIP_TRY(hipMalloc((void **)&m->async_dev, sizeof(AsyncWords)));
+        HIP_TRY(hipMemset(m->async_dev, 0, sizeof(AsyncWords)));
+        HIP_TRY(hipMalloc((void **)&m->probe_flag, kSplitFlagWords * sizeof(unsigned)));
+    }
+    const size_t depth = (size_t)m->opt_async_depth;
+    if (m->async_slots.size() == depth) return MDK_OK;
+    int rc;
+    if ((rc = retire_async(m, true))) return rc;
+    for (auto &sl : m->async_slots) if (sl.done) (void)hipEventDestroy(sl.done);
+    m->async_slots.assign(depth, mdk_gru::AsyncSlot{});
+    m->async_head = m->async_count = 0;
+    m->async_last = nullptr;
+    if (m->async_host) (void)hipHostFree(m->async_host);
+    m->async_host = nullptr;
+    HIP_TRY(hipHostMalloc((void **)&m->async_host, depth * sizeof(AsyncRecord), hipHostMallocDefault));
+    for (auto &sl : m->async_slots) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    return MDK_OK;
+}
+
+// one call, enqueued on `s`; the caller has dropped a batch started ahead, checked the arguments and made room in the ring
+static int enqueue_async_body(mdk_gru *m, const float *x_dev, int B, int T, float *probs_dev, hipStream_t s) {
+    const size_t idx = (m->async_head + m->async_count) % m->async_slots.size();
+    mdk_gru::AsyncSlot &sl = m->async_slots[idx];
+    sl = mdk_gru::AsyncSlot{sl.done};
+    sl.T = T; sl.Tv = T; sl.precision = m->precision;
+    // the workspace is the model's: this call's stream waits (on the device) for the previous call, whatever stream that was on
+    if (m->async_last) HIP_TRY(hipStreamWaitEvent(s, m->async_last, 0));
+    // the back-off counts calls, as in run_forward -- here calls enqueued
+    if (m->split_disabled && m->split_retry_in > 0 && --m->split_retry_in == 0) { m->split_disabled = false; m->learner_epoch++; }
+    sl.epoch = m->learner_epoch;
+    sl.status = m->split_disabled ? MDK_SPLIT_DISABLED : MDK_SPLIT_NOT_USED;
+    SplitPlan sp;
+    int rc;
+    if (!plan_split(m, B, T, sp)) {
+        // not split: the sequential passes, planned with gi so that the range decision is made on the device (run_passes)
+        if ((rc = run_passes(m, x_dev, B, T, probs_dev, s, nullptr, nullptr))) return rc;
+    } else {
+        sl.split = true; sl.S = sp.S; sl.G = sp.G; sl.Tv = sp.Tv;
+        AsyncWords *w = m->async_dev;
+        HIP_TRY(hipMemsetAsync(&w->gate[0], 0, sizeof(AsyncWords) - offsetof(AsyncWords, gate), s));
+        EvTimer tm{m, s};
+        bool need_gi = true;
+        // 1. probe (half precision): the call in fp32-parity mode, its certificate into probe_flag.  Its result lands in probs_dev,
+        //    which the split below overwrites in full (as in run_forward).  A probe of this margin still in flight from an earlier
+        //    call is not repeated: this call is gated on that probe's verdict, which stays in the device words.
+        int probe = 0;
+        if (split_probe_due(m, sp)) {
+            const bool periodic = m->opt_split_audit == 1 && m->opt_split_audit_every > 0 &&
+                                  m->split_calls_since_audit + 1 >= m->opt_split_audit_every;
+            if (!periodic && m->probe_inflight_G == sp.G) {
+                probe = 2;
+            } else {
+                m->precision = MDK_PREC_FP32;
+                rc = split_enqueue(m, sp, x_dev, probs_dev, s, nullptr, nullptr, tm, &need_gi, m->probe_flag);
+                m->precision = MDK_PREC_FP16;
+                if (rc) return rc;
+                probe = 1;
+                sl.probe_ran = true;
+                m->probe_inflight_G = sp.G;
+            }
+        }
+        // 2. the split at the margin in use, its certificate into split_flag
+        if (!m->split_flag) HIP_TRY(hipMalloc((void **)&m->split_flag, kSplitFlagWords * sizeof(unsigned)));
+        if ((rc = split_enqueue(m, sp, x_dev, probs_dev, s, nullptr, nullptr, tm, &need_gi, m->split_flag))) return rc;
+        // 3. the decision
+        hipLaunchKernelGGL(k_split_decide, dim3(1), dim3(64), 0, s, (const unsigned *)m->split_flag, (const unsigned *)m->probe_flag,
+                           8 * (sp.S - 1), m->precision == MDK_PREC_FP16 ? kSplitEpsHalf : kSplitEps, probe, w);
+        // 4. the repair: the sequential passes into probs_dev, empty launches unless the split was rejected.  (Bv * Tv >= B * T: the
+        //    split's workspace holds them -- ensure_workspace allocates nothing after the first call at a shape.)
+        if ((rc = run_passes(m, x_dev, B, T, probs_dev, s, nullptr, nullptr, false, &w->gate[0]))) return rc;
+        // 5. the audit (the first call at a margin / precision, then every "scan_split_audit_every"-th split call ENQUEUED): the
+        //    sequential scan into m->audit, predicated on "certified", compared in full; where it differs by more than the
+        //    tolerance its result is copied over the split's by a predicated kernel
+        const int audit_key = sp.G | (m->precision << 16) | (1 << 24);
+        const bool first = m->split_audited_key != audit_key && m->audit_inflight_key != audit_key;
+        const bool periodic = !first && m->opt_split_audit_every > 0 && ++m->split_calls_since_audit >= m->opt_split_audit_every;
+        if (m->opt_split_audit == 2 || (m->opt_split_audit == 1 && (first || periodic))) {
+            m->split_calls_since_audit = 0;
+            const size_t n = (size_t)B * T * m->desc.num_classes;
+            if (n > m->audit_cap) {
+                free_dev(m->audit); m->audit = nullptr; m->audit_cap = 0;
+                HIP_TRY(hipMalloc((void **)&m->audit, n * sizeof(float)));
+                m->audit_cap = n;
+            }
+            if ((rc = run_passes(m, x_dev, B, T, m->audit, s, nullptr, nullptr, /*lean=*/true, &w->gate[1]))) return rc;
+            const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 256 * 8);
+            hipLaunchKernelGGL(k_split_audit, dim3(blocks), dim3(256), 0, s, (const float *)probs_dev, (const float *)m->audit, n,
+                               &w->rec.audit_bits, (const int *)&w->gate[1]);
+            hipLaunchKernelGGL(k_audit_deliver, dim3(blocks), dim3(256), 0, s, probs_dev, (const float *)m->audit, n,
+                               (const int *)&w->gate[1], (const unsigned *)&w->rec.audit_bits,
+                               m->precision == MDK_PREC_FP16 ? kAuditTolHalf : kAuditTol);
+            sl.audited = true;
+            sl.audit_key = audit_key;
+            m->audit_inflight_key = audit_key;
+        }
+        // 6. the record goes home
+        HIP_TRY(hipMemcpyAsync(&m->async_host[idx], &w->rec, sizeof(AsyncRecord), hipMemcpyDeviceToHost, s));
+        if ((rc = finish_timing(m, tm, s))) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(sl.done, s));
+    m->async_last = sl.done;
+    m->async_count++;
+    return MDK_OK;
+}
+
+// one call, enqueued on `s`; the caller has dropped a batch started ahead, checked the arguments and made room in the ring.  A call
+// that fails part way leaves the bookkeeping as it found it: no slot will ever retire what it would have advanced (an in-flight
+// probe later calls would be gated on, an audit, the cadence and back-off counters)
+static int enqueue_async(mdk_gru *m, const float *x_dev, int B, int T, float *probs_dev, hipStream_t s) {
+    const bool disabled = m->split_disabled;
+    const long retry_in = m->split_retry_in, since_audit = m->split_calls_since_audit, epoch = m->learner_epoch;
+    const int probe_G = m->probe_inflight_G, audit_key = m->audit_inflight_key;
+    const int rc = enqueue_async_body(m, x_dev, B, T, probs_dev, s);
+    if (rc) {
+        m->split_disabled = disabled; m->split_retry_in = retry_in; m->split_calls_since_audit = since_audit; m->learner_epoch = epoch;
+        m->probe_inflight_G = probe_G; m->audit_inflight_key = audit_key;
+    }
+    return rc;
 }

@@ -16,8 +16,10 @@ __global__ __launch_bounds__(256) void k_linear_softmax(
     const float *__restrict__ lin_w,  // [5][64*NCH]
     const float *__restrict__ lin_b,  // [5]
     float *__restrict__ probs,        // [M][5]
-    long M, int normalise)
+    long M, int normalise,
+    const int *__restrict__ gate = nullptr)   // predicated pass (common.hpp gated_off)
 {
+    if (gated_off(gate)) return;
     constexpr int W = 64 * NCH;
     const int lane = threadIdx.x & 63;
     const int sub = lane & 15;
@@ -97,10 +99,12 @@ __global__ __launch_bounds__(256) void k_head_tiled(
     float *__restrict__ probs,        // [B][T][5]
     int B, int T, int n_tiles, int normalise,
     int t0, int nt,                   // columns [t0, t0 + nt) of every window
-    SplitPlan sp)
+    SplitPlan sp,
+    const int *__restrict__ gate = nullptr)   // predicated pass (common.hpp gated_off)
 {
     constexpr int F = DIN * 128;
     __shared__ __attribute__((aligned(16))) float wl[5 * F];
+    if (gated_off(gate)) return;
     for (int i = threadIdx.x; i < 5 * F; i += blockDim.x) wl[i] = lin_w[i];
     __syncthreads();
     const int lane = threadIdx.x & 63;
@@ -172,8 +176,10 @@ template <bool SPLIT>
 static __global__ __launch_bounds__(256) void k_head_combine(
     const float *__restrict__ lpart,  // [D][n_tiles][T][8][5]
     const float *__restrict__ lin_b,  // [5]
-    float *__restrict__ probs, int B, int T, int n_tiles, int D, int normalise, int t0, int nt, SplitPlan sp)
+    float *__restrict__ probs, int B, int T, int n_tiles, int D, int normalise, int t0, int nt, SplitPlan sp,
+    const int *__restrict__ gate)     // predicated pass (common.hpp gated_off)
 {
+    if (gated_off(gate)) return;
     const long total = (long)n_tiles * nt * kTileWin;
     const size_t dir_stride = (size_t)n_tiles * T * 40;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {

@@ -75,7 +75,8 @@ __global__ __launch_bounds__(512, 2) void k_rec_fused(
     float *__restrict__ lpart,             // HEAD: partial logits [D][n_tiles][T][8 windows][5]
     const float *__restrict__ lin_b,       // HEAD = 2: classifier bias [5]
     float *__restrict__ probs,             // HEAD = 2: the result, (nb, T, 5) or the split plan's (B, T, 5)
-    int nb, int normalise, SplitPlan spl)  // HEAD = 2: windows of this pass; softmax or raw logits; spl.S > 1: split scan
+    int nb, int normalise, SplitPlan spl,  // HEAD = 2: windows of this pass; softmax or raw logits; spl.S > 1: split scan
+    const int *__restrict__ gate)          // predicated pass (common.hpp gated_off)
 {
     constexpr bool FIN = HEAD == 2;
     constexpr int DIN = KSTEPS / 4;
@@ -91,6 +92,7 @@ __global__ __launch_bounds__(512, 2) void k_rec_fused(
     // HEAD: this direction's 8 W_lin fragments -- every wave multiplies its step's image by the same ones, once per strip;
     // from LDS instead of eight L2 round trips at the top of every projection phase
     __shared__ half8 wlds[HEAD ? 512 : 1];
+    if (gated_off(gate)) return;
     __builtin_amdgcn_s_setprio(MDK_REC_PRIO);
 
     const int tid = threadIdx.x;

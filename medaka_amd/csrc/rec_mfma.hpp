@@ -77,10 +77,12 @@ __global__ __launch_bounds__(512, 2) void k_rec_mfma(
     float *__restrict__ out,           // act_t (layout.hpp)
     int n_tiles, int T, int D, const float *__restrict__ inv_scale_p, int reverse_mask,
     const int *__restrict__ cond, int want,
-    int s0, int ns)   // steps [s0, s0 + ns) of the scan (scan step s is t = s, or T-1-s when reversed);
+    int s0, int ns,   // steps [s0, s0 + ns) of the scan (scan step s is t = s, or T-1-s when reversed);
                       // s0 > 0 resumes from the h this kernel stored at scan step s0 - 1 (GRU only)
+    const int *__restrict__ gate = nullptr)   // predicated pass (common.hpp gated_off)
 {
     __shared__ __attribute__((aligned(16))) unsigned char hbuf[2 * kHBufBytes];
+    if (gated_off(gate)) return;
     // fused/unfused layer-0 selection is made on the device (input range flag of k_pack_x)
     if (cond != nullptr && ((*cond != 0) != (want != 0))) return;
     // The recurrence is a chain of 2 x T dependent steps: whatever else is resident on this CU -- the side-stream
@@ -495,9 +497,11 @@ static __global__ __launch_bounds__(256) void k_pack_x(
     half8 *__restrict__ xfrag,     // [n_wg][T][kXfragLanes]
     int B, int T, int I, int nq, int hp, int n_wg, float sx, int *__restrict__ oor,
     int t_lo, int nt,              // columns [t_lo, t_lo + nt) of every window (the host path streams x in time slabs)
-    SplitPlan sp)                  // sp.S > 1: B x T is the VIRTUAL batch of a split scan and x the real (sp.B, sp.T, I) one --
+    SplitPlan sp,                  // sp.S > 1: B x T is the VIRTUAL batch of a split scan and x the real (sp.B, sp.T, I) one --
                                    // virtual window v = k * sp.B + w is columns [sp.start[k], +T) of window w (scan_split.hpp)
+    const int *__restrict__ gate)  // predicated pass (common.hpp gated_off)
 {
+    if (gated_off(gate)) return;
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t total = (size_t)n_wg * nt * kXfragLanes;
     if (idx >= total) return;

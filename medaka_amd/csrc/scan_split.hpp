@@ -53,7 +53,9 @@ constexpr float kAuditTolHalf = 4.0e-4f;
 // operands straight from x (k_pack_x); the virtual batch is materialised only for the exact-projection fallback that an input
 // beyond fp16 range switches to on the device (k_pack_x raises the flag).
 static __global__ __launch_bounds__(256) void k_split_gather(const float *__restrict__ x, float *__restrict__ xv,
-                                                             SplitPlan p, int F, int vec, int t_lo, int nt, const int *__restrict__ cond) {
+                                                             SplitPlan p, int F, int vec, int t_lo, int nt, const int *__restrict__ cond,
+                                                             const int *__restrict__ gate) {
+    if (gated_off(gate)) return;          // predicated pass (common.hpp)
     if (cond != nullptr && *cond == 0) return;
     const long row_elems = (long)nt * F / vec;
     const long total = (long)p.S * p.B * row_elems;
@@ -112,7 +114,8 @@ static __global__ __launch_bounds__(128) void k_split_verify(const float *__rest
 // Audit (first certified call of a model, and again whenever its margin has changed): the largest |a - b| over two
 // probability arrays -- the split result against the sequential scan of the same call.  flag[0] = its bit pattern.
 static __global__ __launch_bounds__(256) void k_split_audit(const float *__restrict__ a, const float *__restrict__ b, size_t n,
-                                                            unsigned *__restrict__ flag) {
+                                                            unsigned *__restrict__ flag, const int *__restrict__ gate = nullptr) {
+    if (gated_off(gate)) return;          // predicated audit of the stream-ordered entry: only behind a certified split
     float worst = 0.f;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         float d = fabsf(a[i] - b[i]);
@@ -122,6 +125,61 @@ static __global__ __launch_bounds__(256) void k_split_audit(const float *__restr
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) worst = fmaxf(worst, __shfl_xor(worst, o));
     if ((threadIdx.x & 63) == 0 && worst > 0.f) atomicMax(&flag[0], __float_as_uint(worst));
+}
+
+// ---- the stream-ordered entry (mdk_gru_forward_dev_async, gru_split.hpp): the decision on the device
+// One set of these words per model.  The gates predicate the passes behind the split (common.hpp gated_off); the record is what
+// the host's bookkeeping is later fed from (copied to a page-locked ring slot at the end of the call).
+struct AsyncRecord {
+    float worst;            // largest junction difference of the split (certificate words of k_split_verify)
+    int certified;          // 1: the split is delivered -- its certificate held, and the probe it was gated on (if any)
+    float probe_delta;      // half precision: largest junction difference of the fp32-parity probe the call was gated on
+    int probe_ok;           // ... and that probe's verdict (1 when no probe gated the call)
+    unsigned audit_bits;    // k_split_audit: largest |p_split - p_sequential| (0: not audited, or the split was rejected)
+    int pad[3];
+};
+struct AsyncWords {
+    float probe_delta;      // the last probe's verdict, kept across calls: a later call at its margin is gated on it
+    int probe_ok;
+    int gate[2];            // [0] the repair (sequential passes): 1 = skip, the split is certified; [1] the audit: 1 = skip
+    AsyncRecord rec;        // this call's record -- it and the gates are zeroed at the start of every call
+};
+
+// One wave: reduce the certificate words (and the words of this call's probe, `probe` = 1, or the kept verdict of an earlier
+// call's probe at the same margin, `probe` = 2) against the thresholds, write the gates and the record.  Non-negative floats order
+// like their bit patterns; not-a-number was stored as infinity by k_split_verify.
+static __global__ __launch_bounds__(64) void k_split_decide(const unsigned *__restrict__ flag, const unsigned *__restrict__ probe_flag,
+                                                             int n, float eps, int probe, AsyncWords *__restrict__ w) {
+    const int lane = threadIdx.x;
+    float worst = 0.f, pworst = 0.f;
+    for (int i = lane; i < n; i += 64) {
+        worst = fmaxf(worst, __uint_as_float(flag[i]));
+        if (probe == 1) pworst = fmaxf(pworst, __uint_as_float(probe_flag[i]));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        worst = fmaxf(worst, __shfl_xor(worst, o));
+        pworst = fmaxf(pworst, __shfl_xor(pworst, o));
+    }
+    if (lane != 0) return;
+    if (probe == 1) { w->probe_delta = pworst; w->probe_ok = pworst <= kSplitEps ? 1 : 0; }
+    const bool pok = probe == 0 || w->probe_ok != 0;
+    const bool ok = worst <= eps && pok;
+    w->gate[0] = ok ? 1 : 0;
+    w->gate[1] = ok ? 0 : 1;
+    w->rec.worst = worst;
+    w->rec.certified = ok ? 1 : 0;
+    w->rec.probe_delta = probe ? w->probe_delta : 0.f;
+    w->rec.probe_ok = pok ? 1 : 0;
+}
+
+// A failed audit of the stream-ordered entry: the sequential result replaces the split's in `probs` -- a copy that runs only
+// behind a certified split (`gate`) whose audit found more than `tol` (a hipMemcpyAsync cannot be predicated)
+static __global__ __launch_bounds__(256) void k_audit_deliver(float *__restrict__ probs, const float *__restrict__ audit, size_t n,
+                                                              const int *__restrict__ gate, const unsigned *__restrict__ dp_bits, float tol) {
+    if (gated_off(gate)) return;
+    if (__uint_as_float(__builtin_amdgcn_readfirstlane(*dp_bits)) <= tol) return;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) probs[i] = audit[i];
 }
 
 }  // namespace mdk

@@ -287,6 +287,13 @@ class GruEngine:
             _lib.check(L.mdk_gru_forward_dev(self._h, x_ptr, B, T, out_ptr, stream),
                        "mdk_gru_forward_dev")
 
+    def forward_async_ptr(self, x_ptr, B, T, out_ptr, stream=None):
+        """Stream-ordered device forward (include/medaka_amd.h `mdk_gru_forward_dev_async`): device pointers + hipStream_t.
+        Enqueues the whole call -- the split scan's certificate, the sequential repair of a rejected call, the half-precision
+        probe and the audit are decided on the device -- and returns without waiting for it.  `split()` waits for it."""
+        _lib.check(_lib.load().mdk_gru_forward_dev_async(self._h, x_ptr, B, T, out_ptr, stream),
+                   "mdk_gru_forward_dev_async")
+
     def close(self):
         # a Batcher thread may be inside stage_input: no hand-over targets this engine any more, and the handle is only
         # destroyed once that call has returned

@@ -160,6 +160,9 @@ class GRUModel(CountsMatrixModel):
         self._engine_key = None
         self.exact_kernels = False   # MDK_VARIANT_EXACT (debug cross-check kernels)
         self.kernel_variant = None   # explicit MDK_VARIANT_* override (A/B timing)
+        # forward() on device tensors through the stream-ordered entry: it returns as soon as the call is enqueued on the
+        # current stream, also when the call runs as a split scan ("inside your own PyTorch pipeline")
+        self.stream_ordered = os.environ.get("MEDAKA_AMD_STREAM_ORDERED", "0") == "1"
 
     # -- engine life cycle -----------------------------------------------------------------
     def _state_key(self, dev_index):
@@ -202,7 +205,10 @@ class GRUModel(CountsMatrixModel):
         B, T, _ = x.shape
         out = torch.empty((B, T, 5), dtype=torch.float32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        eng.forward_ptr(x.data_ptr(), B, T, out.data_ptr(), stream=stream)
+        if self.stream_ordered:
+            eng.forward_async_ptr(x.data_ptr(), B, T, out.data_ptr(), stream=stream)
+        else:
+            eng.forward_ptr(x.data_ptr(), B, T, out.data_ptr(), stream=stream)
         return out
 
     def _predict(self, x):

@@ -143,3 +143,76 @@ def decode_consensus(label_probs, symbols="*ACGT", with_gaps=False, with_qualiti
     err = np.clip(1 - probs, 10 ** (-cap / 10.0), 1)
     q = np.minimum(-10 * np.log10(err), cap)
     return seq, (q.astype("u1") + 33).tobytes().decode()
+
+
+def f64_gru_forward(x, state, n_layers=2, bidirectional=True, normalise=True):
+    """The reference's three calls (nn.GRU -> nn.Linear -> softmax, gru.py:58-72) in float64 on the CPU, with the state
+    loaded as given: the high-precision yardstick for models of any width (num_features from W_ih), depth and direction.
+    x: (B, T, F) array -> (B, T, 5) float64 array."""
+    import torch
+
+    x = np.asarray(x)
+    state = {k: torch.as_tensor(np.asarray(v, dtype=np.float64)) for k, v in state.items()}
+    gru_size = state["gru.weight_hh_l0"].shape[1]
+    gru = torch.nn.GRU(state["gru.weight_ih_l0"].shape[1], gru_size, num_layers=n_layers, bidirectional=bidirectional,
+                       batch_first=True).double()
+    linear = torch.nn.Linear((2 if bidirectional else 1) * gru_size, state["linear.weight"].shape[0]).double()
+    gru.load_state_dict({k[len("gru."):]: v for k, v in state.items() if k.startswith("gru.")}, strict=True)
+    linear.load_state_dict({k[len("linear."):]: v for k, v in state.items() if k.startswith("linear.")}, strict=True)
+    with torch.inference_mode():
+        y = linear(gru(torch.as_tensor(x, dtype=torch.float64))[0])
+        if normalise:
+            y = torch.softmax(y, dim=-1)
+    return y.numpy()
+
+
+def arch_state(num_features, n_layers, bidirectional, gain=2.5, seed=0, head_gain=7.0):
+    """Seeded weights for any GRUModel architecture: uniform in +-1/sqrt(128) as PyTorch draws them, W_hh times `gain` and
+    linear.weight times `head_gain`, so that the softmax rows are confident enough for argmax checks (near-uniform rows
+    hide errors).  Returns {state_dict name: float32 array}."""
+    rng = np.random.default_rng(1000003 * seed + 1009 * num_features + 31 * n_layers + int(bool(bidirectional)))
+    H, D = 128, 2 if bidirectional else 1
+    k = 1.0 / np.sqrt(H)
+    st = {}
+    for layer in range(n_layers):
+        kin = num_features if layer == 0 else D * H
+        for sfx in ([""] + (["_reverse"] if bidirectional else [])):
+            st[f"gru.weight_ih_l{layer}{sfx}"] = rng.uniform(-k, k, (3 * H, kin)).astype(np.float32)
+            st[f"gru.weight_hh_l{layer}{sfx}"] = (rng.uniform(-k, k, (3 * H, H)) * gain).astype(np.float32)
+            st[f"gru.bias_ih_l{layer}{sfx}"] = rng.uniform(-k, k, 3 * H).astype(np.float32)
+            st[f"gru.bias_hh_l{layer}{sfx}"] = rng.uniform(-k, k, 3 * H).astype(np.float32)
+    st["linear.weight"] = (rng.uniform(-k, k, (5, D * H)) * head_gain).astype(np.float32)
+    st["linear.bias"] = rng.uniform(-k, k, 5).astype(np.float32)
+    return st
+
+
+def padded_state(state, num_features, pad="zero", seed=0):
+    """A 2-layer bidirectional state of 10 features (`weights_trained`) widened to `num_features` (11..16): the columns
+    appended to gru.weight_ih_l0{,_reverse} are zeros (`pad="zero"`) or small random values (`pad="random"`)."""
+    rng = np.random.default_rng(seed)
+    out = {k: np.asarray(v, dtype=np.float32).copy() for k, v in state.items()}
+    for key in ("gru.weight_ih_l0", "gru.weight_ih_l0_reverse"):
+        w = out[key]
+        extra = num_features - w.shape[1]
+        assert extra >= 0, (key, w.shape, num_features)
+        cols = (np.zeros((w.shape[0], extra)) if pad == "zero"
+                else rng.uniform(-0.1, 0.1, (w.shape[0], extra))).astype(np.float32)
+        out[key] = np.ascontiguousarray(np.concatenate([w, cols], axis=1))
+    return out
+
+
+def arch_input(x10, num_features, pad=None, seed=0):
+    """(B, T, 10) normalised counts -> (B, T, num_features): the first columns for num_features <= 10; beyond 10 the
+    appended columns are `pad` if given (e.g. 0.0), else further columns of counts drawn like the first ones (uniform
+    in [0, 1) mixed with the existing columns, so that every feature carries signal)."""
+    x10 = np.asarray(x10, dtype=np.float32)
+    if num_features <= x10.shape[-1]:
+        return np.ascontiguousarray(x10[..., :num_features])
+    extra = num_features - x10.shape[-1]
+    if pad is not None:
+        cols = np.full(x10.shape[:-1] + (extra,), pad, dtype=np.float32)
+    else:
+        rng = np.random.default_rng(seed)
+        src = x10[..., rng.integers(0, x10.shape[-1], extra)]
+        cols = (0.5 * src + 0.5 * rng.random(src.shape)).astype(np.float32)
+    return np.ascontiguousarray(np.concatenate([x10, cols], axis=-1))

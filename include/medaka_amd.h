@@ -43,12 +43,14 @@ typedef struct mdk_gru mdk_gru;
 
 /*
  * Architecture of reference `GRUModel.__init__` (medaka/architectures/gru.py:13-56).
- * Supported: hidden == 128, 1 <= num_layers <= 4, bidirectional 0/1, num_features <= 256,
+ * Supported: hidden == 128, 1 <= num_layers <= 4, bidirectional 0/1, num_features <= 256 (> 16: MDK_VARIANT_EXACT only),
+ * or hidden == 256 (the default of `medaka train`, reference models.py DEFAULT_MODEL_DICT), 1 <= num_layers <= 4,
+ * bidirectional 0/1, num_features <= 16: cluster recurrence, sequential scans only,
  * num_classes == 5 (the reference hard-codes Linear(.., 5), gru.py:53-55).
  */
 typedef struct {
     int num_features;  /* 10: channels a c g t A C G T d D (src/medaka_counts.h:19-30) */
-    int hidden;        /* gru_size, 128 for every bundled consensus / variant model */
+    int hidden;        /* gru_size: 128 (every bundled consensus / variant model) or 256 */
     int num_layers;    /* 2 */
     int bidirectional; /* 1 */
     int num_classes;   /* 5: '*ACGT' (medaka/labels.py:342) */
@@ -273,7 +275,11 @@ int mdk_gru_set_normalise(mdk_gru *m, int normalise);
  *                                                   only: no kernel can run beside recurrences that hold every CU),
  *                                                   as one copy behind the forward otherwise
  *   "max_rows_per_pass"    = 0 (16 Mi) | n          column budget (B*T) of one pass over the workspace;
- *                                                   larger batches run as equal passes
+ *                                                   larger batches run as equal passes (hidden 256: default 8 Mi,
+ *                                                   10 KB per column of a bidirectional model)
+ *   "wide_wait_ms"         = 3000 | 0..60000        hidden 256: wall-clock budget of the host's re-runs of a forward whose
+ *                                                   cluster recurrence timed out (another tenant holding CUs) before
+ *                                                   MDK_ERR_DEVICE
  *   "async_depth"          = 8 | 1..64              mdk_gru_forward_dev_async: the most calls whose records are not yet retired;
  *                                                   at the limit a new call waits for the oldest one (the entry's only host
  *                                                   wait in the steady state)

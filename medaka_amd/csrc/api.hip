@@ -24,6 +24,7 @@
 #include "rec_mfma.hpp"
 #include "rec_fused.hpp"
 #include "scan_split.hpp"
+#include "gru_wide.hpp"
 
 using namespace mdk;
 
@@ -40,6 +41,7 @@ extern "C" const char *mdk_version(void) { return "medaka_amd 0.1 (gfx950)"; }
 // The GRU engine proper, in four parts of this translation unit (each builds on the one before):
 #include "gru_model.hpp"     // model object, contexts, create / destroy / options
 #include "gru_pass.hpp"      // PassPlan + Pass: one pass of the network over a batch
+#include "gru_wide_run.hpp"  // the GRU(256) forward: cluster recurrences, sequential scans
 #include "gru_split.hpp"     // split scan: plan, enqueue / finish, run_forward, start_call
 #include "gru_entries.hpp"   // mdk_gru_forward_dev / _stage_input / _forward_pipelined / _forward / counts, decoded
 

@@ -65,6 +65,10 @@ struct LayerDev {
     half8 *wih_frag = nullptr;    // [D][8 waves][K/32][3 gates][2][64] (layers >= 1)
     float *inv_scale_rec = nullptr;  // [D]
     float *inv_scale_gi = nullptr;   // [D]
+    // GRU(256) (gru_wide.hpp) uses whh_frag [D][64 tiles][8 ks][2][64], layer 0: w_ih_t [D][F][768] fp32, layers >= 1: wih_frag
+    // [D][48 tiles][K/32][2][64], all gi columns permuted and pre-scaled; bias_gi [D][768], b_hn [D][256], inv_scale_rec [D], and
+    float wide_alpha[2] = {0.f, 0.f};   // layers >= 1: gi = (A W_ih^T) * alpha + bias, alpha = S / (a_scale * swi)
+    float wide_a_scale = 0.f;           // layers >= 1: activation scale of the projection's fp16 split
 };
 
 // Everything ONE call in flight owns: workspace, flags, streams, event pools.  A model has two of these (mdk_gru below): the
@@ -212,6 +216,15 @@ struct mdk_gru : Ctx {
     int probe_inflight_G = 0;                // margin of the probe whose verdict sits in async_dev and is not yet retired (0: none)
     int audit_inflight_key = 0;              // audit key of an audit enqueued and not yet retired
     long learner_epoch = 0;                  // bumped by every retirement that moves the margin learner or the back-off (retire_one)
+    // GRU(256) (gru_wide.hpp, gru_wide_run.hpp): sequential scans only, one context, its own workspace
+    bool wide = false;
+    float *wgi = nullptr;                    // [D][rows][768]
+    float *wact[2] = {nullptr, nullptr};     // [rows][D * 256]
+    size_t wrows = 0;
+    unsigned long long *wexch = nullptr;     // [D][kGExchPerDir] granules + headers
+    int *wstatus = nullptr;                  // [0] != 0: a cluster timed out
+    int n_cus = 0;
+    int opt_wide_wait_ms = 3000;             // wall-clock budget of re-runs after a cluster time-out before MDK_ERR_DEVICE ("wide_wait_ms")
 };
 
 
@@ -294,6 +307,7 @@ extern "C" void mdk_gru_destroy(mdk_gru *m) {
     }
     free_dev(m->wlin_frag);
     free_dev(m->lin_w); free_dev(m->lin_b);
+    free_dev(m->wgi); free_dev(m->wact[0]); free_dev(m->wact[1]); free_dev(m->wexch); free_dev(m->wstatus);
     (void)hipDeviceSynchronize();
     if (m->shares_copy_streams) { free_ctx(static_cast<Ctx &>(*m)); free_ctx(m->other); }
     else { free_ctx(m->other); free_ctx(static_cast<Ctx &>(*m)); }
@@ -304,16 +318,83 @@ extern "C" void mdk_gru_destroy(mdk_gru *m) {
     delete m;
 }
 
+// GRU(256) layer (gru_wide.hpp): W_hh as the A-fragments k_gru_wide keeps in registers -- tile nt = member * 8 + wave, row n of
+// the tile = gate (n & 3) of unit 32 * member + 4 * wave + (n >> 2), gate 3 = zero -- and W_ih in the permuted gi order, column
+// j' = 3 * unit + gate: layer 0 (K = F <= 16) as fp32 [D][K][768] for k_gi_wide0, layers >= 1 as the B-fragments of k_gemm_rows.
+// gi and the bias are pre-scaled by S = kActScale * sw like the accumulator (a power of two: exact in fp32).
+static int build_wide_gru_layer(LayerDev &Ld, int K, int D, const float *const *w) {
+    const bool first = K <= 16;                        // layer 0 (layers >= 1 have K = 256 or 512)
+    const int KS = first ? 0 : K / 32;
+    Ld.K = K;
+    Ld.wide_a_scale = kActScale;                       // layers >= 1: h in (-1, 1)
+    std::vector<half8> whh((size_t)D * 64 * kGKS * 2 * 64), wih((size_t)D * 48 * KS * 2 * 64);
+    std::vector<float> bias((size_t)D * kGG), bhn((size_t)D * kGH), inv_rec(D), w0(first ? (size_t)D * K * kGG : 0);
+    for (int d = 0; d < D; ++d) {
+        const float *w_ih = w[4 * d + 0], *w_hh = w[4 * d + 1], *b_ih = w[4 * d + 2], *b_hh = w[4 * d + 3];
+        const float sw = pick_scale(w_hh, (size_t)kGG * kGH), swi = pick_scale(w_ih, (size_t)kGG * K);
+        const float up = kActScale * sw;
+        inv_rec[d] = 1.0f / up;
+        Ld.wide_alpha[d] = up / (Ld.wide_a_scale * swi);
+        for (int u = 0; u < kGH; ++u) bhn[(size_t)d * kGH + u] = b_hh[2 * kGH + u];
+        for (int jp = 0; jp < kGG; ++jp) {
+            const int j = (jp % 3) * kGH + jp / 3;
+            bias[(size_t)d * kGG + jp] = (b_ih[j] + (jp % 3 < 2 ? b_hh[j] : 0.0f)) * up;
+            if (first)
+                for (int k = 0; k < K; ++k) w0[((size_t)d * K + k) * kGG + jp] = w_ih[(size_t)j * K + k] * up;
+        }
+        for (int nt = 0; nt < 64; ++nt)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int n = lane & 15, kg = lane >> 4, gate = n & 3;
+                const int j = gate * kGH + 32 * (nt / 8) + 4 * (nt % 8) + (n >> 2);
+                for (int ks = 0; ks < kGKS; ++ks) {
+                    half8 hi, lo;
+                    for (int i = 0; i < 8; ++i) {
+                        _Float16 a = (_Float16)0.f, b = (_Float16)0.f;
+                        if (gate < 3) split_host(w_hh[(size_t)j * kGH + 32 * ks + 8 * kg + i] * sw, a, b);
+                        hi[i] = a; lo[i] = b;
+                    }
+                    const size_t base = ((((size_t)d * 64 + nt) * kGKS + ks) * 2) * 64 + lane;
+                    whh[base] = hi; whh[base + 64] = lo;
+                }
+            }
+        for (int nt = 0; nt < 48; ++nt)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int jp = nt * 16 + (lane & 15), kg = lane >> 4;
+                const int j = (jp % 3) * kGH + jp / 3;
+                for (int ks = 0; ks < KS; ++ks) {
+                    half8 hi, lo;
+                    for (int i = 0; i < 8; ++i) {
+                        const int k = 32 * ks + 8 * kg + i;
+                        _Float16 a, b;
+                        split_host(w_ih[(size_t)j * K + k] * swi, a, b);
+                        hi[i] = a; lo[i] = b;
+                    }
+                    const size_t base = ((((size_t)d * 48 + nt) * KS + ks) * 2) * 64 + lane;
+                    wih[base] = hi; wih[base + 64] = lo;
+                }
+            }
+    }
+    int rc;
+    if ((rc = upload(&Ld.whh_frag, whh))) return rc;
+    if (first && (rc = upload(&Ld.w_ih_t, w0))) return rc;
+    if (!first && (rc = upload(&Ld.wih_frag, wih))) return rc;
+    if ((rc = upload(&Ld.bias_gi, bias))) return rc;
+    if ((rc = upload(&Ld.b_hn, bhn))) return rc;
+    if ((rc = upload(&Ld.inv_scale_rec, inv_rec))) return rc;
+    return MDK_OK;
+}
+
 // The classifier: Linear(D * 128 -> 5) as fp32 (k_head_tiled, the exact kernels) and, for the head fused into the last
 // layer's kernel (rec_fused.hpp HEAD), as fp16 hi/lo B-fragments per direction: k = hidden unit in the A image's order
 // (slot (ks, lane-group gq, i) = unit 32 ks + 8 gq + i), column n = class (columns 5..15 zero).
 static int upload_classifier(mdk_gru *m, const float *lin_w, const float *lin_b) {
-    const int D = m->D, H = kH, C = m->desc.num_classes;
+    const int D = m->D, H = m->desc.hidden, C = m->desc.num_classes;
     int rc;
     std::vector<float> lw(lin_w, lin_w + (size_t)C * D * H);
     std::vector<float> lb(lin_b, lin_b + C);
     if ((rc = upload(&m->lin_w, lw))) return rc;
     if ((rc = upload(&m->lin_b, lb))) return rc;
+    if (m->wide) return MDK_OK;             // (no fused head at 256: k_linear_softmax reads lin_w)
     const float swl = pick_scale(lw.data(), lw.size());
     m->lin_inv_scale = 1.0f / (kActScale * swl);
     std::vector<half8> wl((size_t)D * 4 * 2 * 64);
@@ -340,7 +421,8 @@ extern "C" int mdk_gru_create(const mdk_gru_desc *desc, const float *const *weig
     *out = nullptr;
     const int I = desc->num_features, H = desc->hidden, L = desc->num_layers;
     const int D = desc->bidirectional ? 2 : 1, C = desc->num_classes;
-    if (H != kH) return fail(MDK_ERR_ARG, "unsupported gru_size %d (engine supports 128)", H);
+    if (H != kH && H != kGH) return fail(MDK_ERR_ARG, "unsupported gru_size %d (engine supports 128 and 256)", H);
+    if (H == kGH && (I < 1 || I > 16)) return fail(MDK_ERR_ARG, "unsupported num_features %d for gru_size 256 (1..16)", I);
     if (L < 1 || L > 4) return fail(MDK_ERR_ARG, "unsupported num_layers %d (1..4)", L);
     if (I < 1 || I > 256) return fail(MDK_ERR_ARG, "unsupported num_features %d (1..256)", I);
     if (C != 5) return fail(MDK_ERR_ARG, "unsupported num_classes %d (reference Linear is fixed at 5)", C);
@@ -357,6 +439,7 @@ extern "C" int mdk_gru_create(const mdk_gru_desc *desc, const float *const *weig
     m->device = device;
     m->D = D;
     m->layers.resize(L);
+    m->wide = H == kGH;
     // process-wide defaults of the split scan (the options of the same names override them per model)
     if (const char *e = getenv("MDK_SCAN_SPLIT")) m->opt_scan_split = std::min(std::max(atoi(e), 0), kMaxSplit);
     if (const char *e = getenv("MDK_SCAN_SPLIT_ADAPT")) m->opt_split_adapt = std::max(atoi(e), 0);
@@ -371,7 +454,25 @@ extern "C" int mdk_gru_create(const mdk_gru_desc *desc, const float *const *weig
     auto bail = [&](int code) { mdk_gru_destroy(m); return code; };
     if ((rc = init_ctx(m))) return bail(rc);
 
-    for (int l = 0; l < L; ++l) {
+    for (int l = 0; l < L && m->wide; ++l)
+        if ((rc = build_wide_gru_layer(m->layers[l], l == 0 ? I : D * H, D, weights + 4 * l * D))) return bail(rc);
+    if (m->wide) {
+        HIP_TRY(hipMalloc((void **)&m->wexch, (size_t)D * kGExchPerDir * sizeof(unsigned long long)));
+        HIP_TRY(hipMalloc((void **)&m->wstatus, 64));
+        HIP_TRY(hipMemset(m->wstatus, 0, 64));
+        for (int hp = 0; hp < 2; ++hp) {
+            HIP_TRY(hipFuncSetAttribute(hp ? reinterpret_cast<const void *>(&k_gemm_rows<16, true, 48>)
+                                           : reinterpret_cast<const void *>(&k_gemm_rows<16, false, 48>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 16 * 4 * kWGemmBlk));
+            HIP_TRY(hipFuncSetAttribute(hp ? reinterpret_cast<const void *>(&k_gemm_rows<8, true, 48>)
+                                           : reinterpret_cast<const void *>(&k_gemm_rows<8, false, 48>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 8 * 4 * kWGemmBlk));
+        }
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, device));
+        m->n_cus = prop.multiProcessorCount;
+    }
+    for (int l = 0; l < L && !m->wide; ++l) {
         LayerDev &Ld = m->layers[l];
         const int K = (l == 0) ? I : D * H;
         Ld.K = K;
@@ -517,6 +618,7 @@ extern "C" int mdk_gru_set_precision(mdk_gru *m, int precision) {
 extern "C" int mdk_gru_set_variant(mdk_gru *m, int variant) {
     if (!m) return fail(MDK_ERR_ARG, "null model");
     if (variant != MDK_VARIANT_MFMA && variant != MDK_VARIANT_EXACT) return fail(MDK_ERR_ARG, "bad variant %d", variant);
+    if (variant == MDK_VARIANT_EXACT && m->wide) return fail(MDK_ERR_ARG, "MDK_VARIANT_EXACT supports gru_size 128 only");
     if (variant != m->variant) { (void)hipSetDevice(m->device); drop_pending(m); }
     m->variant = variant;
     return MDK_OK;
@@ -589,6 +691,9 @@ extern "C" int mdk_gru_set_option(mdk_gru *m, const char *key, int value) {
     } else if (!strcmp(key, "async_depth")) {
         if (value < 1 || value > 64) return fail(MDK_ERR_ARG, "async_depth must be 1..64");
         m->opt_async_depth = value;              // (drop_pending above has retired every call in flight: the ring is resized by the next call)
+    } else if (!strcmp(key, "wide_wait_ms")) {
+        if (value < 0 || value > 60000) return fail(MDK_ERR_ARG, "wide_wait_ms must be 0..60000");
+        m->opt_wide_wait_ms = value;             // (gru_size 256: how long a cluster time-out is retried; no effect at 128)
     } else if (!strcmp(key, "scan_split_margin")) {
         if (value < 16 || value > 4096 || value % 8) return fail(MDK_ERR_ARG, "scan_split_margin must be a multiple of 8 in 16..4096");
         m->opt_split_margin = value;

@@ -120,6 +120,7 @@ struct PassPlan {
     // the host entries) lets the throughput regime run WITHOUT gi and without those launches; if the flag is up it marks
     // the model (`oor_seen`) and repeats the call -- from then on with gi and the device-side decision.
     bool need_gi = true;
+    bool wide = false;         // GRU(256): sequential cluster scans, nothing fused or overlapped (gru_wide_run.hpp)
 };
 
 static int plan_pass(const mdk_gru *m, int nb, int T, const HostIO *io, const SplitPlan *sp, PassPlan &P, bool host_checks_range = false,
@@ -132,6 +133,15 @@ static int plan_pass(const mdk_gru *m, int nb, int T, const HostIO *io, const Sp
     P.io_out = io && io->p_host && !sp;
     P.sp_out = sp && io && io->p_host;          // split call: `probs` is the real (B, T, C) result, io->p_host the caller's buffer
     if (P.exact) return MDK_OK;
+    if (m->desc.hidden == kGH) {
+        if (m->layers[0].K > 16) return fail(MDK_ERR_ARG, "num_features %d > 16 is not supported at gru_size 256", m->layers[0].K);
+        P.hp = (m->precision == MDK_PREC_FP16);
+        const WidePlan w = plan_wide(nb, P.D, P.hp, m->opt_gpu_share);
+        P.wide = true;
+        P.nq = w.gw / 4;
+        P.n_wg = w.work_groups;
+        return MDK_OK;
+    }
     if (m->layers[0].K > 16)
         return fail(MDK_ERR_ARG, "num_features %d > 16 is only supported by MDK_VARIANT_EXACT", m->layers[0].K);
 #ifdef MDK_DEBUG_HOOKS
@@ -794,8 +804,11 @@ static int finish_timing(mdk_gru *m, EvTimer &tm, hipStream_t s) {
 // all passes of one call; x_host / probs_host (may be null) select the streamed host path per pass.  `lean`: plan for the
 // regime without gi (plan_pass); the CALLER looks at the range flag afterwards (range_flag_raised) and repeats without it.
 // `gate` (device-resident x and probabilities only): every kernel of the passes is predicated on it (Pass::gate)
+static int run_wide_passes(mdk_gru *m, const float *x_dev, int B, int T, float *probs_dev, hipStream_t s, const float *x_host,
+                           float *probs_host, const int *gate);
 static int run_passes(mdk_gru *m, const float *x_dev, int B, int T, float *probs_dev, hipStream_t s,
                       const float *x_host, float *probs_host, bool lean = false, const int *gate = nullptr) {
+    if (m->wide) return run_wide_passes(m, x_dev, B, T, probs_dev, s, x_host, probs_host, gate);
     memset(&m->last, 0, sizeof(m->last));
     m->last.n_layers = m->desc.num_layers;
     // windows per pass, bounded so that the workspace stays within a fixed column budget

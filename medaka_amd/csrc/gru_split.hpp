@@ -57,8 +57,10 @@ extern "C" int mdk_pass_plan(const mdk_gru_desc *desc, int precision, int gpu_sh
                              int mode, mdk_pass_shape *out) {
     if (!desc || !out) return fail(MDK_ERR_ARG, "null argument");
     if (windows < 1 || T < 1 || gpu_share < 1 || gpu_share > 8 || split_chunks < 0 || split_chunks > kMaxSplit ||
-        (precision != MDK_PREC_FP32 && precision != MDK_PREC_FP16) || desc->num_layers < 1 || desc->num_features < 1)
-        return fail(MDK_ERR_ARG, "bad argument (windows=%d T=%d gpu_share=%d split_chunks=%d precision=%d)", windows, T, gpu_share, split_chunks, precision);
+        (precision != MDK_PREC_FP32 && precision != MDK_PREC_FP16) || desc->num_layers < 1 || desc->num_features < 1 ||
+        (desc->hidden != kH && desc->hidden != kGH))
+        return fail(MDK_ERR_ARG, "bad argument (windows=%d T=%d gpu_share=%d split_chunks=%d precision=%d hidden=%d; hidden 128 or 256)",
+                    windows, T, gpu_share, split_chunks, precision, desc->hidden);
     mdk_gru m;
     m.desc = *desc;
     m.D = desc->bidirectional ? 2 : 1;
@@ -103,6 +105,7 @@ static bool plan_split(const mdk_gru *m, int B, int T, SplitPlan &p) {
     static const int env_abl = getenv("MDK_ABLATE") ? atoi(getenv("MDK_ABLATE")) : 0;
     p.S = 1;
     if (m->opt_scan_split == 0 || (m->split_disabled && m->opt_scan_split == 1)) return false;
+    if (m->wide) return false;             // GRU(256): sequential scans only
     if (m->variant != MDK_VARIANT_MFMA || m->D != 2 || m->desc.num_layers != 2 || m->opt_ablate || env_abl) return false;
     if (m->layers[0].K > 16) return false;
     return plan_split_shape(B, T, m->opt_gpu_share, m->opt_scan_split, m->margin.cur ? m->margin.cur : m->opt_split_margin,
@@ -440,7 +443,8 @@ static int run_forward(mdk_gru *m, const float *x_dev, int B, int T, float *prob
 static int start_call(mdk_gru *m, const float *x_dev, int B, int T, float *probs_dev, hipStream_t s, float *probs_host,
                       mdk_gru::Started *st, const Ctx *prev) {
     st->valid = false;
-    if (m->timing || m->variant != MDK_VARIANT_MFMA) return MDK_OK;
+    // (GRU(256): a cluster recurrence tolerates no second forward beside it, and its time-out is read on the host)
+    if (m->timing || m->variant != MDK_VARIANT_MFMA || m->wide) return MDK_OK;
     SplitPlan sp;
     int rc;
     // (the back-off of a model whose certificate was rejected at the largest margin counts calls in run_forward: a call that

@@ -399,12 +399,14 @@ __global__ __launch_bounds__(512, 1) void k_lstm_wide(
 constexpr int kWGemmRows = 64;
 constexpr int kWGemmBlk = kWGemmRows * 16 + 16;   // one (k-step, lane-group) block of an image + pad
 
-template <int KS, bool HP = false>   // HP: one fp16 product, hi image only
+// NT: column tiles of 16 -- 96 = the LSTM's 1536 columns, 48 = the GRU(256)'s 768 (gru_wide.hpp); chunks of 3 per wave.
+template <int KS, bool HP = false, int NT = 96>   // HP: one fp16 product, hi image only
 __global__ __launch_bounds__(512, 1) void k_gemm_rows(
     const float *__restrict__ A, const half8 *__restrict__ wfrag, const float *__restrict__ bias,
     float *__restrict__ out, int T, int t_begin, int t_len, float a_scale, float alpha)   // rows (window blockIdx.y,
                                                                                             // t in [t_begin, t_begin + t_len))
 {
+    static_assert(NT % 24 == 0, "8 waves x chunks of 3 column tiles");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int K = 32 * KS;
     constexpr int IMG = KS * 4 * kWGemmBlk;
@@ -436,8 +438,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm_rows(
     __syncthreads();
 
 #pragma unroll 1
-    for (int chunk = 0; chunk < 4; ++chunk) {
-        const int nt0 = w8 * 12 + chunk * 3;
+    for (int chunk = 0; chunk < NT / 24; ++chunk) {
+        const int nt0 = w8 * (NT / 8) + chunk * 3;
         floatx4 acc[4][3];
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
@@ -477,7 +479,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_rows(
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const long row = row0 + mt * 16 + 4 * g + r;
-                    if (row < M) out[(size_t)row * kWG4 + colj] = __builtin_fmaf(acc[mt][j][r], alpha, bv);
+                    if (row < M) out[(size_t)row * (NT * 16) + colj] = __builtin_fmaf(acc[mt][j][r], alpha, bv);
                 }
         }
     }

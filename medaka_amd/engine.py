@@ -33,10 +33,11 @@ def split_plan(B, T, gpu_share=1, scan_split=1, margin=128):
 
 
 def pass_plan(windows, T, num_features=10, num_layers=2, bidirectional=True, half=False, gpu_share=1, host_in=False,
-              host_out=False, split_chunks=0, host_checks_range=False, lean=False, out_of_range_seen=False):
+              host_out=False, split_chunks=0, host_checks_range=False, lean=False, out_of_range_seen=False, gru_size=128):
     """How a pass of `windows` windows of T columns would be launched (include/medaka_amd.h `mdk_pass_plan`; no device needed):
-    work-group granularity, what is fused / streamed, and whether the gi workspace is needed."""
-    desc = _lib.GruDesc(int(num_features), 128, int(num_layers), int(bool(bidirectional)), 5, 1)
+    work-group granularity, what is fused / streamed, and whether the gi workspace is needed.  `gru_size` = 256: the
+    sequential cluster scan (work_groups = CUs it holds), nothing fused or streamed."""
+    desc = _lib.GruDesc(int(num_features), int(gru_size), int(num_layers), int(bool(bidirectional)), 5, 1)
     t = _lib.PassShape()
     mode = (1 if host_checks_range else 0) | (2 if lean else 0) | (4 if out_of_range_seen else 0)
     _lib.check(_lib.load().mdk_pass_plan(ctypes.byref(desc), 1 if half else 0, int(gpu_share), int(windows), int(T),

@@ -29,7 +29,7 @@ logger = logging.getLogger("medaka_amd")
 def _gru_supported(model):
     """Every limit of mdk_gru_create and of the production kernels (include/medaka_amd.h), so that an
     unsupported archive keeps the reference model instead of failing at the first forward."""
-    return (getattr(model, "gru_size", None) == 128 and 1 <= getattr(model, "num_features", 10) <= 16
+    return (getattr(model, "gru_size", None) in (128, 256) and 1 <= getattr(model, "num_features", 10) <= 16
             and 1 <= getattr(model, "n_layers", 2) <= 4)
 
 
@@ -105,7 +105,7 @@ def convert(model, device=None, strict=None):
         return model
     if name == "GRUModel":
         if not _gru_supported(model):
-            return _keep_reference(model, "outside the engine's envelope (gru_size 128, 1-4 layers, <= 16 features)", strict)
+            return _keep_reference(model, "outside the engine's envelope (gru_size 128 or 256, 1-4 layers, <= 16 features)", strict)
         kwargs = model.to_dict()["kwargs"]
         kwargs.pop("time_steps", None)
         kwargs.pop("classify_activation", None)

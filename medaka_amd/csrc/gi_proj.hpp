@@ -9,6 +9,7 @@
 // Both write gi in the tile-major register order of the recurrence kernel (layout.hpp); the
 // GEMM also reads the previous layer's activations in that order, so both are streaming kernels
 // over contiguous blocks.
+//  * k_gemm_rows: layers of the cluster recurrences (cluster.hpp), natural row order.
 // The folded bias is b_ih + b_hh for the r and z gates and b_ih for n (b_hn must stay inside
 // the r * (.) product, see rec_mfma.hpp).
 #pragma once
@@ -247,6 +248,100 @@ __global__ __launch_bounds__(512, MT <= 4 ? 4 : 2) void k_gi_gemm(
                     store_run<NG>(dst, v);      // the NG gates of (unit, window) are adjacent (layout.hpp)
                 }
             }
+        }
+    }
+}
+
+// gi = (A W^T) * alpha + bias for the wide recurrences (lstm_wide.hpp, gru_wide.hpp): A fp32 [M][32*KS] natural rows, W pre-packed
+// as fp16 hi/lo B-fragments in the PERMUTED column order k_lstm_wide reads ([96 tiles][KS][2][64]),
+// fp16x2 split with three products, fp32 accumulate.  Work-group = 64 rows (one contiguous run of
+// A) x all 1536 columns: A is converted once into LDS (hi and lo images, 16-byte fragments), the
+// 8 waves walk 12 column tiles each in chunks of 3 with B streaming from L2.
+constexpr int kWGemmRows = 64;
+constexpr int kWGemmBlk = kWGemmRows * 16 + 16;   // one (k-step, lane-group) block of an image + pad
+
+// NT: column tiles of 16 -- 96 = the LSTM(384)'s 1536 columns, 48 = the GRU(256)'s 768; chunks of 3 per wave.
+template <int KS, bool HP = false, int NT = 96>   // HP: one fp16 product, hi image only
+__global__ __launch_bounds__(512, 1) void k_gemm_rows(
+    const float *__restrict__ A, const half8 *__restrict__ wfrag, const float *__restrict__ bias,
+    float *__restrict__ out, int T, int t_begin, int t_len, float a_scale, float alpha)   // rows (window blockIdx.y,
+                                                                                            // t in [t_begin, t_begin + t_len))
+{
+    static_assert(NT % 24 == 0, "8 waves x chunks of 3 column tiles");
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    constexpr int K = 32 * KS;
+    constexpr int IMG = KS * 4 * kWGemmBlk;
+    unsigned char *ahi = lds, *alo = lds + IMG;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 15, g = lane >> 4;
+    const long row0 = (long)blockIdx.y * T + t_begin + (long)blockIdx.x * kWGemmRows;
+    const long M = (long)blockIdx.y * T + t_begin + t_len;   // first row beyond this window's range
+
+    for (int it = tid; it < kWGemmRows * 4 * KS; it += 512) {
+        const int row = it / (4 * KS), k8 = it % (4 * KS);
+        float4 x0 = make_float4(0.f, 0.f, 0.f, 0.f), x1 = x0;
+        if (row0 + row < M) {
+            const float4 *src = reinterpret_cast<const float4 *>(A + (size_t)(row0 + row) * K + k8 * 8);
+            x0 = src[0]; x1 = src[1];
+        }
+        const float xv[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+        half8 hi, lo;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            _Float16 a, b;
+            split_f16(xv[i] * a_scale, a, b);
+            hi[i] = a; lo[i] = b;
+        }
+        *reinterpret_cast<half8 *>(ahi + k8 * kWGemmBlk + row * 16) = hi;
+        if constexpr (!HP) *reinterpret_cast<half8 *>(alo + k8 * kWGemmBlk + row * 16) = lo;
+    }
+    __syncthreads();
+
+#pragma unroll 1
+    for (int chunk = 0; chunk < NT / 24; ++chunk) {
+        const int nt0 = w8 * (NT / 8) + chunk * 3;
+        floatx4 acc[4][3];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) acc[mt][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+        for (int ks = 0; ks < KS; ++ks) {
+            half8 bh[3], bl[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const half8 *wp = wfrag + (((size_t)(nt0 + j) * KS + ks) * 2) * 64 + lane;
+                bh[j] = wp[0];
+                if constexpr (!HP) bl[j] = wp[64];
+            }
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                const int off = (ks * 4 + g) * kWGemmBlk + (mt * 16 + c) * 16;
+                const half8 ah = *reinterpret_cast<const half8 *>(ahi + off);
+                half8 al;
+                if constexpr (!HP) al = *reinterpret_cast<const half8 *>(alo + off);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    acc[mt][j] = mfma16(ah, bh[j], acc[mt][j]);
+                    if constexpr (!HP) {
+                        acc[mt][j] = mfma16(al, bh[j], acc[mt][j]);
+                        acc[mt][j] = mfma16(ah, bl[j], acc[mt][j]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int colj = (nt0 + j) * 16 + c;
+            const float bv = bias[colj];
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const long row = row0 + mt * 16 + 4 * g + r;
+                    if (row < M) out[(size_t)row * (NT * 16) + colj] = __builtin_fmaf(acc[mt][j][r], alpha, bv);
+                }
         }
     }
 }

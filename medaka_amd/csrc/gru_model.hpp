@@ -221,7 +221,7 @@ struct mdk_gru : Ctx {
     float *wgi = nullptr;                    // [D][rows][768]
     float *wact[2] = {nullptr, nullptr};     // [rows][D * 256]
     size_t wrows = 0;
-    unsigned long long *wexch = nullptr;     // [D][kGExchPerDir] granules + headers
+    unsigned long long *wexch = nullptr;     // [D][wide_exch_words(256)] granules + headers
     int *wstatus = nullptr;                  // [0] != 0: a cluster timed out
     int n_cus = 0;
     int opt_wide_wait_ms = 3000;             // wall-clock budget of re-runs after a cluster time-out before MDK_ERR_DEVICE ("wide_wait_ms")
@@ -318,9 +318,8 @@ extern "C" void mdk_gru_destroy(mdk_gru *m) {
     delete m;
 }
 
-// GRU(256) layer (gru_wide.hpp): W_hh as the A-fragments k_gru_wide keeps in registers -- tile nt = member * 8 + wave, row n of
-// the tile = gate (n & 3) of unit 32 * member + 4 * wave + (n >> 2), gate 3 = zero -- and W_ih in the permuted gi order, column
-// j' = 3 * unit + gate: layer 0 (K = F <= 16) as fp32 [D][K][768] for k_gi_wide0, layers >= 1 as the B-fragments of k_gemm_rows.
+// GRU(256) layer (gru_wide.hpp): W_hh as the A-fragments k_gru_wide keeps in registers (pack_wide_tiles, gate 3 = zero rows)
+// and W_ih in the permuted gi order, column j' = 3 * unit + gate: layer 0 (K = F <= 16) as fp32 [D][K][768] for k_gi_wide0, layers >= 1 as the B-fragments of k_gemm_rows.
 // gi and the bias are pre-scaled by S = kActScale * sw like the accumulator (a power of two: exact in fp32).
 static int build_wide_gru_layer(LayerDev &Ld, int K, int D, const float *const *w) {
     const bool first = K <= 16;                        // layer 0 (layers >= 1 have K = 256 or 512)
@@ -342,21 +341,7 @@ static int build_wide_gru_layer(LayerDev &Ld, int K, int D, const float *const *
             if (first)
                 for (int k = 0; k < K; ++k) w0[((size_t)d * K + k) * kGG + jp] = w_ih[(size_t)j * K + k] * up;
         }
-        for (int nt = 0; nt < 64; ++nt)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int n = lane & 15, kg = lane >> 4, gate = n & 3;
-                const int j = gate * kGH + 32 * (nt / 8) + 4 * (nt % 8) + (n >> 2);
-                for (int ks = 0; ks < kGKS; ++ks) {
-                    half8 hi, lo;
-                    for (int i = 0; i < 8; ++i) {
-                        _Float16 a = (_Float16)0.f, b = (_Float16)0.f;
-                        if (gate < 3) split_host(w_hh[(size_t)j * kGH + 32 * ks + 8 * kg + i] * sw, a, b);
-                        hi[i] = a; lo[i] = b;
-                    }
-                    const size_t base = ((((size_t)d * 64 + nt) * kGKS + ks) * 2) * 64 + lane;
-                    whh[base] = hi; whh[base + 64] = lo;
-                }
-            }
+        pack_wide_tiles(whh.data() + (size_t)d * 64 * kGKS * 2 * 64, w_hh, kGH, kGH, 3, sw);
         for (int nt = 0; nt < 48; ++nt)
             for (int lane = 0; lane < 64; ++lane) {
                 const int jp = nt * 16 + (lane & 15), kg = lane >> 4;
@@ -457,7 +442,7 @@ extern "C" int mdk_gru_create(const mdk_gru_desc *desc, const float *const *weig
     for (int l = 0; l < L && m->wide; ++l)
         if ((rc = build_wide_gru_layer(m->layers[l], l == 0 ? I : D * H, D, weights + 4 * l * D))) return bail(rc);
     if (m->wide) {
-        HIP_TRY(hipMalloc((void **)&m->wexch, (size_t)D * kGExchPerDir * sizeof(unsigned long long)));
+        HIP_TRY(hipMalloc((void **)&m->wexch, (size_t)D * wide_exch_words(kGH) * sizeof(unsigned long long)));
         HIP_TRY(hipMalloc((void **)&m->wstatus, 64));
         HIP_TRY(hipMemset(m->wstatus, 0, 64));
         for (int hp = 0; hp < 2; ++hp) {

@@ -136,7 +136,7 @@ static int plan_pass(const mdk_gru *m, int nb, int T, const HostIO *io, const Sp
     if (m->desc.hidden == kGH) {
         if (m->layers[0].K > 16) return fail(MDK_ERR_ARG, "num_features %d > 16 is not supported at gru_size 256", m->layers[0].K);
         P.hp = (m->precision == MDK_PREC_FP16);
-        const WidePlan w = plan_wide(nb, P.D, P.hp, m->opt_gpu_share);
+        const WidePlan w = plan_gru_wide(nb, P.D, P.hp, m->opt_gpu_share);
         P.wide = true;
         P.nq = w.gw / 4;
         P.n_wg = w.work_groups;

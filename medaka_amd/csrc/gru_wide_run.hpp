@@ -3,18 +3,15 @@
 // Part of api.hip (included there after gru_pass.hpp).
 #pragma once
 
-constexpr int kGPF = 3;     // gi prefetch ring depth of k_gru_wide (k_lstm_wide's MDK_WIDE_PF)
-
 // one forward over nb windows; *timed_out = a cluster's exchange or placement handshake timed out (the result is lost)
 static int wide_pass_once(mdk_gru *m, const float *x, int nb, int T, float *probs, hipStream_t s, int *timed_out) {
     const int D = m->D, L = m->desc.num_layers;
     const bool hp = m->precision == MDK_PREC_FP16;
-    const WidePlan w = plan_wide(nb, D, hp, m->opt_gpu_share);
+    const WidePlan w = plan_gru_wide(nb, D, hp, m->opt_gpu_share);
     *timed_out = 0;
     if (w.work_groups > m->n_cus)
         return fail(MDK_ERR_DEVICE, "the GRU(256) cluster recurrence needs %d co-resident work-groups, the device has %d CUs",
                     w.work_groups, m->n_cus);
-    const unsigned gx = 8u * kGC * (unsigned)((w.n_clusters + 7) / 8);
     const float *in = x;
     for (int l = 0; l < L; ++l) {
         const LayerDev &Ld = m->layers[l];
@@ -39,10 +36,10 @@ static int wide_pass_once(mdk_gru *m, const float *x, int nb, int T, float *prob
 #undef MDK_GGEMM
         }
         // (tags restart at 1 in every launch: last launch's granules and placement headers must not look current)
-        HIP_TRY(hipMemsetAsync(m->wexch, 0, (size_t)D * kGExchPerDir * sizeof(unsigned long long), s));
+        HIP_TRY(hipMemsetAsync(m->wexch, 0, (size_t)D * wide_exch_words(kGH) * sizeof(unsigned long long), s));
         const int poll = hp ? 14 : 7;            // one group per cluster: 64-clock sleeps before the first poll (as rl_lstm384)
 #define MDK_GREC(NG, HPF)                                                                                            \
-    hipLaunchKernelGGL((k_gru_wide<kGPF, NG, HPF>), dim3(gx, (unsigned)D), dim3(512), 0, s, (const float *)m->wgi, \
+    hipLaunchKernelGGL((k_gru_wide<kWidePF, NG, HPF>), dim3((unsigned)w.grid, (unsigned)D), dim3(512), 0, s, (const float *)m->wgi, \
                        Ld.whh_frag, Ld.b_hn, Ld.inv_scale_rec, outp, m->wexch, m->wstatus, nb, T, D, w.n_clusters,     \
                        w.n_units, poll, 1)
         if (hp) { if (w.ngrp == 2) MDK_GREC(2, true); else MDK_GREC(1, true); }
@@ -60,32 +57,18 @@ static int wide_pass_once(mdk_gru *m, const float *x, int nb, int T, float *prob
         hipLaunchKernelGGL(k_linear_softmax<4>, dim3((unsigned)blocks), dim3(256), 0, s, in, m->lin_w, m->lin_b, probs, M,
                            m->desc.normalise, (const int *)nullptr);
     HIP_TRY(hipGetLastError());
-    int st = 0;
-    HIP_TRY(hipMemcpyAsync(&st, m->wstatus, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (st != 0) {
-        HIP_TRY(hipMemsetAsync(m->wstatus, 0, sizeof(int), s));
-        *timed_out = 1;
-    }
-    return MDK_OK;
+    return take_wide_status(m->wstatus, s, timed_out);
 }
 
-// A time-out is handled as rl_lstm384's (rl_api.hip rl_forward_wide): the forward is re-run with a growing pause -- 20, 40, ...
-// 320 ms -- until it goes through or "wide_wait_ms" (3 s by default) of wall clock are spent; only then MDK_ERR_DEVICE.  Never a hang, never a wrong result.
+// A time-out is retried with growing pauses for up to "wide_wait_ms" (3 s by default), then MDK_ERR_DEVICE (retry_wide).
 static int wide_pass(mdk_gru *m, const float *x, int nb, int T, float *probs, hipStream_t s) {
-    const auto t0 = std::chrono::steady_clock::now();
-    int timed_out = 0, pause_ms = 0, tries = 0;
-    for (;;) {
-        tries++;
-        int rc = wide_pass_once(m, x, nb, T, probs, s, &timed_out);
-        if (rc || !timed_out) return rc;
-        const long spent = (long)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
-        pause_ms = pause_ms ? std::min(2 * pause_ms, 320) : 20;
-        if (spent + pause_ms > m->opt_wide_wait_ms)
-            return fail(MDK_ERR_DEVICE, "GRU(256) cluster exchange timed out %d times in %ld ms: the recurrence needs %d CUs of the GPU "
-                                        "at once", tries, spent, plan_wide(nb, m->D, m->precision == MDK_PREC_FP16, m->opt_gpu_share).work_groups);
-        std::this_thread::sleep_for(std::chrono::milliseconds(pause_ms));
-    }
+    return retry_wide([&](int *timed_out) { return wide_pass_once(m, x, nb, T, probs, s, timed_out); },
+                      [&](int tries, long spent) {
+                          return fail(MDK_ERR_DEVICE, "GRU(256) cluster exchange timed out %d times in %ld ms: the recurrence needs %d CUs of "
+                                                      "the GPU at once", tries, spent,
+                                      plan_gru_wide(nb, m->D, m->precision == MDK_PREC_FP16, m->opt_gpu_share).work_groups);
+                      },
+                      m->opt_wide_wait_ms, std::chrono::steady_clock::now());
 }
 
 // run_passes for a GRU(256) model: the same column budget per pass; x and the probabilities cross PCIe whole (host entries)

@@ -3,9 +3,6 @@
 // MFMA recurrence / projection kernels as the GRU model (CELL = 1, four gate tiles) -> head.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
-#include <thread>
-
 #include <cstdlib>
 #include <cstring>
 
@@ -22,9 +19,6 @@ using namespace mdk;
 
 #ifndef MDK_PF
 #define MDK_PF 5
-#endif
-#ifndef MDK_WIDE_PF
-#define MDK_WIDE_PF 3
 #endif
 
 namespace {
@@ -187,8 +181,8 @@ static int build_lstm_layer(LstmLayer &Ld, int K, int D, int reverse_mask, const
 }
 
 // Wide layer: w_ih is [1536][K] (K = 128 for the folded first layer, 384 after), w_hh [1536][384],
-// bias [1536] already summed.  Gate columns are permuted into the order k_lstm_wide's waves own:
-// tile nt = member * 8 + wave, column n of the tile = gate (n & 3) of unit 32*member + 4*wave + (n >> 2).
+// bias [1536] already summed.  Gate columns are permuted into the order k_lstm_wide's waves own (pack_wide_tiles):
+// column n of tile nt = gate (n & 3) of unit 4 * nt + (n >> 2).
 static int build_wide_layer(WideLayer &Ld, int K, const float *w_ih, const float *w_hh, const float *bias,
                             float a_scale, int reverse) {
     Ld.KS = K / 32; Ld.reverse = reverse; Ld.a_scale = a_scale;
@@ -199,34 +193,9 @@ static int build_wide_layer(WideLayer &Ld, int K, const float *w_ih, const float
     Ld.alpha = up_rec / (a_scale * swi);
     std::vector<half8> whh((size_t)96 * kWKS * 2 * 64), wih((size_t)96 * Ld.KS * 2 * 64);
     std::vector<float> bp(kWG4);
-    for (int nt = 0; nt < 96; ++nt) {
-        const int member = nt / 8, w8 = nt % 8;
-        for (int lane = 0; lane < 64; ++lane) {
-            const int n = lane & 15, kg = lane >> 4;
-            const int j = (n & 3) * kWH + 32 * member + 4 * w8 + (n >> 2);
-            if (kg == 0) bp[nt * 16 + n] = bias[j] * up_rec;
-            for (int ks = 0; ks < kWKS; ++ks) {
-                half8 hi, lo;
-                for (int i = 0; i < 8; ++i) {
-                    _Float16 a, b;
-                    split_host(w_hh[(size_t)j * kWH + 32 * ks + 8 * kg + i] * sw, a, b);
-                    hi[i] = a; lo[i] = b;
-                }
-                const size_t base = (((size_t)nt * kWKS + ks) * 2) * 64 + lane;
-                whh[base] = hi; whh[base + 64] = lo;
-            }
-            for (int ks = 0; ks < Ld.KS; ++ks) {
-                half8 hi, lo;
-                for (int i = 0; i < 8; ++i) {
-                    _Float16 a, b;
-                    split_host(w_ih[(size_t)j * K + 32 * ks + 8 * kg + i] * swi, a, b);
-                    hi[i] = a; lo[i] = b;
-                }
-                const size_t base = (((size_t)nt * Ld.KS + ks) * 2) * 64 + lane;
-                wih[base] = hi; wih[base + 64] = lo;
-            }
-        }
-    }
+    for (int jp = 0; jp < kWG4; ++jp) bp[jp] = bias[(jp & 3) * kWH + jp / 4] * up_rec;
+    pack_wide_tiles(whh.data(), w_hh, kWH, kWH, 4, sw);
+    pack_wide_tiles(wih.data(), w_ih, kWH, K, 4, swi);
     int rc;
     if ((rc = upload(&Ld.whh_frag, whh))) return rc;
     if ((rc = upload(&Ld.wih_frag, wih))) return rc;
@@ -359,7 +328,7 @@ extern "C" int mdk_rl_create(const mdk_rl_desc *desc, const float *const *w, int
                                        (i % 2 == 0) ? 1 : 0)))
                 return bail(rc);
         }
-        HIP_TRY(hipMalloc((void **)&m->exch, kWExchWords * sizeof(unsigned long long)));
+        HIP_TRY(hipMalloc((void **)&m->exch, wide_exch_words(kWH) * sizeof(unsigned long long)));
         HIP_TRY(hipMalloc((void **)&m->status, 64));
         HIP_TRY(hipMemset(m->status, 0, 64));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_rows<12, false>),
@@ -501,14 +470,8 @@ static int rl_forward_wide_once(mdk_rl *m, const unsigned char *x_dev, int B, in
     else hipLaunchKernelGGL((k_rl_front<false, false>), dim3((P + kRlPos - 1) / kRlPos, B), dim3(256), 0, s, fa);
     if (m->timing) HIP_TRY(hipEventRecord(m->tev[2], s));
 
-    // groups of 8 windows (16 in half precision); up to 16 groups: one per cluster; more: two interleaved
-    const int gw = hp ? 2 * kWWin : kWWin;
-    const int n_groups = (B + gw - 1) / gw;
-    int ngrp = n_groups > kWMaxClusters ? 2 : 1;
-    if (m->opt_wide_groups == 1 || m->opt_wide_groups == 2) ngrp = m->opt_wide_groups;
-    const int n_units = (n_groups + ngrp - 1) / ngrp;
-    const int n_clusters = std::min(n_units, kWMaxClusters);
-    const unsigned rec_grid = 8u * kWC * (unsigned)((n_clusters + 7) / 8);
+    // up to 16 groups: one per cluster; more: two interleaved
+    const WidePlan w = plan_wide(B, hp, kWC, kWMaxClusters, m->opt_wide_groups);
     // The stack is uni-directional, so the next layer's projection of column t only needs this
     // layer's h_t: each layer's recurrence runs as kChunks resumable launches and, behind every
     // chunk, the next layer's k_gemm_rows for the columns just produced runs on a side stream, on the
@@ -520,9 +483,9 @@ static int rl_forward_wide_once(mdk_rl *m, const unsigned char *x_dev, int B, in
         HIP_TRY(hipGetDeviceProperties(&prop, m->device));
         m->n_cus = prop.multiProcessorCount;
     }
-    if ((int)rec_grid > m->n_cus)
-        return fail(MDK_ERR_DEVICE, "the LSTM(384) cluster recurrence needs %u co-resident work-groups, the device has %d CUs",
-                    rec_grid, m->n_cus);
+    if (w.grid > m->n_cus)
+        return fail(MDK_ERR_DEVICE, "the LSTM(384) cluster recurrence needs %d co-resident work-groups, the device has %d CUs",
+                    w.grid, m->n_cus);
     const bool ovl = allow_overlap && m->opt_overlap && P >= 1024;
     const int n_chunks = ovl ? kChunks : 1;
     auto launch_gemm = [&](const WideLayer &Lg, const float *src, float *gi_out, hipStream_t st, int t_begin, int t_len) {
@@ -546,29 +509,14 @@ static int rl_forward_wide_once(mdk_rl *m, const unsigned char *x_dev, int B, in
         for (int j = 0; j < n_chunks; ++j) {
             const int s0 = (int)((long)P * j / n_chunks) / 8 * 8;
             const int s1 = (j + 1 == n_chunks) ? P : (int)((long)P * (j + 1) / n_chunks) / 8 * 8;
-            HIP_TRY(hipMemsetAsync(m->exch, 0, kWExchWords * sizeof(unsigned long long), s));
-#define MDK_WIDE_N(NG, HPF, ABLV)                                                                        \
-    hipLaunchKernelGGL((k_lstm_wide<MDK_WIDE_PF, NG, HPF, ABLV>), dim3(rec_grid), dim3(512), 0, s, gi_cur, Ld.whh_frag, \
-                       outp, m->exch, m->status, B, P, Ld.reverse, Ld.inv_rec, n_clusters, n_units, m->opt_force_wt, \
+            HIP_TRY(hipMemsetAsync(m->exch, 0, wide_exch_words(kWH) * sizeof(unsigned long long), s));
+#define MDK_WIDE(NG, HPF)                                                                                                  \
+    hipLaunchKernelGGL((k_lstm_wide<kWidePF, NG, HPF>), dim3((unsigned)w.grid), dim3(512), 0, s, gi_cur, Ld.whh_frag, outp, \
+                       m->exch, m->status, B, P, Ld.reverse, Ld.inv_rec, w.n_clusters, w.n_units, m->opt_force_wt,         \
                        hp ? 2 * m->opt_poll_delay : m->opt_poll_delay, s0, s1 - s0, m->cstate, m->opt_async ? 0 : 1)   /* half: fewer MFMAs, later stores */
-#define MDK_WIDE(ABLV)                                                                                   \
-    do {                                                                                                 \
-        if (hp) { if (ngrp == 2) MDK_WIDE_N(2, true, ABLV); else MDK_WIDE_N(1, true, ABLV); }            \
-        else { if (ngrp == 2) MDK_WIDE_N(2, false, ABLV); else MDK_WIDE_N(1, false, ABLV); }             \
-    } while (0)
-#ifdef MDK_WIDE_ABLATE   // timing experiments only (profiles/): MDK_WIDE_ABL selects a garbage-result variant
-            switch (getenv("MDK_WIDE_ABL") ? atoi(getenv("MDK_WIDE_ABL")) : 0) {
-                case 1: MDK_WIDE(1); break;
-                case 2: MDK_WIDE(2); break;
-                case 4: MDK_WIDE(4); break;
-                case 8: MDK_WIDE(8); break;
-                default: MDK_WIDE(0);
-            }
-#else
-            MDK_WIDE(0);
-#endif
+            if (hp) { if (w.ngrp == 2) MDK_WIDE(2, true); else MDK_WIDE(1, true); }
+            else { if (w.ngrp == 2) MDK_WIDE(2, false); else MDK_WIDE(1, false); }
 #undef MDK_WIDE
-#undef MDK_WIDE_N
             if (!has_next) continue;
             const int t_begin = Ld.reverse ? P - s1 : s0;
             if (ovl) {
@@ -592,25 +540,15 @@ static int rl_forward_wide_once(mdk_rl *m, const unsigned char *x_dev, int B, in
     }
     HIP_TRY(hipGetLastError());
     if (m->opt_async) return MDK_OK;        // status is read by the next call or by mdk_rl_check()
-    // the cluster recurrence spins across work-groups with bounded waits: read the time-out flag
-    int st = 0;
-    HIP_TRY(hipMemcpyAsync(&st, m->status, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (st != 0) {
-        HIP_TRY(hipMemsetAsync(m->status, 0, sizeof(int), s));
-        *timed_out = 1;
-    }
-    return MDK_OK;
+    return take_wide_status(m->status, s, timed_out);   // the cluster recurrence spins with bounded waits
 }
 
 // The cluster exchange needs every member of a cluster on a CU at the same time.  A time-out (a late
 // member: another tenant on the GPU, or the side-stream projection competing for CUs) is not an error
-// yet: the layer stack is run once more on the plain schedule -- nothing on the side stream, one launch
-// per layer.  If that times out as well somebody else is holding CUs: every try is bounded on the device (50 ms of
-// wall clock in the placement handshake, every later launch of a lost forward returns at once), so the HOST keeps
-// retrying the plain schedule with a growing pause -- 20, 40, ... 320 ms -- until the forward goes through or
-// "wide_wait_ms" (3 s by default) of wall clock are spent; only then MDK_ERR_DEVICE.  A co-tenant or a long foreign
-// kernel that holds the CUs for a few hundred milliseconds is waited out; a GPU that cannot host the kernel at all
+// yet: the layer stack is run once more at once on the plain schedule -- nothing on the side stream, one
+// launch per layer.  If that times out as well somebody else is holding CUs, and the plain schedule is
+// retried with growing pauses for up to "wide_wait_ms" (retry_wide): a co-tenant or a long foreign kernel
+// that holds the CUs for a few hundred milliseconds is waited out; a GPU that cannot host the kernel at all
 // is reported after the budget, not after minutes of spinning and never with a wrong result.
 static int rl_forward_wide(mdk_rl *m, const unsigned char *x_dev, int B, int P, int Dp, int F,
                            float *probs_dev, hipStream_t s) {
@@ -628,22 +566,18 @@ static int rl_forward_wide(mdk_rl *m, const unsigned char *x_dev, int B, int P, 
     if (rc) return rc;
     rc = rl_forward_wide_once(m, x_dev, B, P, Dp, F, probs_dev, s, true, &timed_out);
     if (rc || !timed_out) return rc;
-    int pause_ms = 0, tries = 1;
-    for (;;) {
-        m->wide_retries++;
-        tries++;
-        if ((rc = inject())) return rc;
-        timed_out = 0;
-        rc = rl_forward_wide_once(m, x_dev, B, P, Dp, F, probs_dev, s, false, &timed_out);
-        if (rc || !timed_out) return rc;
-        const long spent = (long)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
-        pause_ms = pause_ms ? std::min(2 * pause_ms, 320) : 20;
-        if (spent + pause_ms > m->opt_wait_ms)
+    return retry_wide(
+        [&](int *to) {
+            m->wide_retries++;
+            const int rc2 = inject();
+            return rc2 ? rc2 : rl_forward_wide_once(m, x_dev, B, P, Dp, F, probs_dev, s, false, to);
+        },
+        [&](int tries, long spent) {
             return fail(MDK_ERR_DEVICE, "LSTM(384) cluster exchange timed out %d times in %ld ms (the later tries without the "
                                         "overlapped projection): the rl_lstm384 path needs %d CUs of the GPU to itself",
                         tries, spent, 8 * kWC * 2);
-        std::this_thread::sleep_for(std::chrono::milliseconds(pause_ms));
-    }
+        },
+        m->opt_wait_ms, t0, 1);
 }
 
 // asynchronous mode ("wide_async" = 1): surfaces a time-out of an earlier mdk_rl_forward_dev
@@ -651,14 +585,10 @@ extern "C" int mdk_rl_check(mdk_rl *m, void *stream) {
     if (!m) return fail(MDK_ERR_ARG, "null model");
     if (!m->wide || !m->status) return MDK_OK;
     HIP_TRY(hipSetDevice(m->device));
-    int st = 0;
-    HIP_TRY(hipMemcpyAsync(&st, m->status, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    if (st != 0) {
-        HIP_TRY(hipMemsetAsync(m->status, 0, sizeof(int), (hipStream_t)stream));
-        return fail(MDK_ERR_DEVICE, "LSTM(384) cluster exchange timed out in an earlier asynchronous forward");
-    }
-    return MDK_OK;
+    int raised = 0;
+    const int rc = take_wide_status(m->status, (hipStream_t)stream, &raised);
+    if (rc || !raised) return rc;
+    return fail(MDK_ERR_DEVICE, "LSTM(384) cluster exchange timed out in an earlier asynchronous forward");
 }
 
 static int rl_forward_dev_inner(mdk_rl *m, const unsigned char *x_dev, int B, int P, int Dp, int F,

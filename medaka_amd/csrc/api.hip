@@ -38,11 +38,12 @@ using namespace mdk;
 extern "C" const char *mdk_last_error(void) { return g_mdk_err.c_str(); }
 extern "C" const char *mdk_version(void) { return "medaka_amd 0.1 (gfx950)"; }
 
-// The GRU engine proper, in four parts of this translation unit (each builds on the one before):
+// The GRU engine proper, in parts of this translation unit (each builds on the ones before):
+#include "split_policy.hpp"  // the split scan's call-level policy: margin learner, back-off, probe, audits (host only)
 #include "gru_model.hpp"     // model object, contexts, create / destroy / options
 #include "gru_pass.hpp"      // PassPlan + Pass: one pass of the network over a batch
 #include "gru_wide_run.hpp"  // the GRU(256) forward: cluster recurrences, sequential scans
-#include "gru_split.hpp"     // split scan: plan, enqueue / finish, run_forward, start_call
+#include "gru_split.hpp"     // split scan: plan, enqueue / finish, run_forward, start_call, enqueue_async / retire_one
 #include "gru_entries.hpp"   // mdk_gru_forward_dev / _stage_input / _forward_pipelined / _forward / counts, decoded
 
 // ------------------------------------------------------------------------------------------

@@ -145,13 +145,7 @@ static int try_early_start(mdk_gru *m, unsigned long long token, int B, int T, f
     if (!m->opt_early_start || !next_probs_host || m->pending.st.valid || m->timing) return MDK_OK;
     // a call that the learner will move (a smaller margin on trial) or that an audit / probe will repeat is not worth starting:
     // its plan is not known before the current call has been judged
-    const int g_now = m->margin.cur ? m->margin.cur : m->opt_split_margin;
-    if (m->opt_scan_split == 1 && m->opt_split_adapt > 0 && m->margin.quiet + 2 >= m->opt_split_adapt &&
-        split_margin_down(g_now, m->margin.floor_) != 0) return MDK_OK;
-    if (m->margin.trial_back) return MDK_OK;
-    if (m->opt_scan_split && m->opt_split_audit == 1 &&
-        (m->split_audited_key == 0 || (m->opt_split_audit_every > 0 && m->split_calls_since_audit + 2 >= m->opt_split_audit_every))) return MDK_OK;
-    if (m->opt_split_audit == 2) return MDK_OK;
+    if (m->policy.next_plan_may_move()) return MDK_OK;
     mdk_gru::StageSlot *sl = nullptr;
     {
         std::lock_guard<std::mutex> lock(m->stage_mu);

@@ -1,54 +1,6 @@
-// The model object of the consensus GRU engine: margin learner, weights, the two contexts, create / destroy / options.
-// Part of api.hip (one translation unit; included there, in this order: gru_model, gru_pass, gru_split, gru_entries).
+// The model object of the consensus GRU engine: weights, the two contexts, the split scan's policy, create / destroy / options.
+// Part of api.hip (one translation unit; included there, in this order: split_policy, gru_model, gru_pass, gru_split, gru_entries).
 #pragma once
-// ---- the margin of the split scan, learned per model (scan_split.hpp).  Pure state machine, no
-// device: also exported as mdk_margin_sim for the CPU property tests.
-// The margins a model can learn: a ladder instead of doublings (a set that needs 192 should not pay for 256: 19 % of all
-// columns against 25 %).  Margins outside the ladder (option "scan_split_margin") join it at the next rung.
-static const int kMarginLadder[] = {64, 96, 128, 192, 256, 384, 512};
-static int split_margin_up(int G) {
-    for (int r : kMarginLadder) if (r > G) return r;
-    return 2 * kSplitMarginMax;                      // above the ladder: the caller gives the model up
-}
-static int split_margin_down(int G, int floor_) {
-    int best = 0;
-    for (int r : kMarginLadder) if (r < G && r >= floor_) best = r;
-    return best;                                     // 0: nothing smaller is allowed
-}
-struct MarginLearner {
-    int cur = 0;          // margin in use (0: the option's starting margin)
-    int floor_ = 0;       // no shrink below this: one rung above the largest margin a certificate was ever rejected at
-    int quiet = 0;        // consecutive certified calls at the current margin whose differences sat at the noise floor
-    int trial_back = 0;   // != 0: the current margin is a shrink on trial; a rejection returns to this one
-    enum Next { RETRY = 0, GIVE_UP = 1 };
-    void reset(bool forget_rejections) { cur = quiet = trial_back = 0; if (forget_rejections) floor_ = 0; }
-    // a certified call at margin G; returns the margin a kept trial came from (0: none).  `adapt` = quiet calls before a smaller
-    // margin is tried (0: never), `noise_floor` = largest junction difference that still counts as quiet
-    int certified(int G, float worst, float noise_floor, int adapt) {
-        const int was = trial_back;
-        trial_back = 0;
-        quiet = worst <= noise_floor ? quiet + 1 : 0;
-        if (adapt > 0 && quiet >= adapt) {
-            const int down = split_margin_down(G, floor_);
-            quiet = 0;
-            if (down) { trial_back = G; cur = down; }
-        }
-        return was;
-    }
-    // a rejected certificate at margin G: RETRY = run the call again at `cur` (a failed trial goes back, anything else one rung
-    // up), GIVE_UP = nothing larger is left.  `*back` = 1 if this was a trial
-    Next rejected(int G, int *back) {
-        quiet = 0;
-        floor_ = std::max(floor_, split_margin_up(G));          // never shrink to a rejected margin again
-        *back = 0;
-        if (trial_back) { cur = trial_back; trial_back = 0; *back = 1; return RETRY; }
-        const int next = split_margin_up(G);
-        if (next > kSplitMarginMax) return GIVE_UP;
-        cur = next;
-        return RETRY;
-    }
-};
-
 // ------------------------------------------------------------------------------------------
 // model object
 struct LayerDev {
@@ -138,25 +90,7 @@ struct mdk_gru : Ctx {
     int opt_deferred_store = 1;              // recurrence: HBM store of h_t from inside step t+1 (rec_mfma.hpp DS)
     int opt_gpu_share = 1;                   // processes sharing this GPU (launch.py --procs-per-gpu): divides the CU budgets below
     int opt_stream_host = 1;                 // host path: x in / probabilities out in time slabs under the recurrences
-    // split scan (scan_split.hpp)
-    int opt_scan_split = 1;                  // 0 off, 1 auto, n >= 2: n chunks per window whenever the shape allows it
-    int opt_split_margin = 128;              // G: columns of warm-up on either side of a chunk (where the model starts)
-    MarginLearner margin;                    // the margin in use, LEARNED per model: one rung up the ladder 64 .. 512 on a rejected
-                                             // certificate, one rung down after `opt_split_adapt` certified calls at the noise floor
-    int opt_split_adapt = 8;                 // certified calls at the noise floor before a smaller margin is tried (0: never shrink)
-    // half precision: a margin is used only after a call CERTIFIED AT IT IN FP32-PARITY MODE (a "probe": the same call, run once
-    // more with the hi/lo operands, threshold 2^-18, result discarded) -- half mode's own certificate compares fp16 images of h
-    // (threshold 2^-10) and cannot see an un-merged state below ~1e-3; see run_forward
-    int opt_split_probe = 1;                 // 0: half mode trusts its own certificate (round 5's behaviour)
-    std::vector<int> probed_ok;              // margins a probe certified
-    long probes_done = 0;
-    float probe_last_delta = 0.f;
-    bool split_disabled = false;             // a certificate failed at the largest margin (or an audit failed): sequential scans (auto mode)
-    long split_retry_in = 0;                 // ... for this many calls; then one more try at the largest margin (0: for good -- failed audits)
-    long split_backoff = 0;                  // the last back-off (doubles per rejection at the largest margin: 64 .. 4096 calls)
-    mdk_gru_split last_split{};
-    int opt_split_audit = 1;                 // 0 never, 1 the first certified call of every margin, 2 every certified call
-    int split_audited_key = 0;               // margin | precision << 16 whose first certified call has been audited (0 = none yet)
+    SplitPolicy policy;                      // split scan (scan_split.hpp): options, margin learner, back-off, probe, audits, last call
     float *audit = nullptr;                  // the sequential scan's probabilities of an audited call
     size_t audit_cap = 0;
     // early hand-over of the next batch (mdk_gru_stage_input): its host -> device copy runs on `stage_stream` while the
@@ -170,12 +104,6 @@ struct mdk_gru : Ctx {
     long staged_used = 0;
     int stage_unredeemed = 0;                // slots overwritten in a row whose token nobody had redeemed
     int stage_pause = 0;                     // > 0: the next this many hand-overs are skipped (nobody was redeeming them)
-    // standing audit: every `opt_split_audit_every`-th certified call is ALSO run as the sequential scan (run_forward)
-    int opt_split_audit_every = 256;
-    long split_calls_since_audit = 0;
-    long audits_done = 0;
-    int audit_failures = 0;
-    float audit_worst = 0.f;
     // timing
     bool timing = false;
     // the NEXT batch's forward, enqueued ahead of its call (mdk_gru_forward_pipelined): lives in `other` while valid
@@ -213,9 +141,6 @@ struct mdk_gru : Ctx {
     std::vector<AsyncSlot> async_slots;
     size_t async_head = 0, async_count = 0;  // oldest slot not yet retired, slots in flight
     hipEvent_t async_last = nullptr;         // behind the last call: the next one's stream waits for it (the workspace is shared)
-    int probe_inflight_G = 0;                // margin of the probe whose verdict sits in async_dev and is not yet retired (0: none)
-    int audit_inflight_key = 0;              // audit key of an audit enqueued and not yet retired
-    long learner_epoch = 0;                  // bumped by every retirement that moves the margin learner or the back-off (retire_one)
     // GRU(256) (gru_wide.hpp, gru_wide_run.hpp): sequential scans only, one context, its own workspace
     bool wide = false;
     float *wgi = nullptr;                    // [D][rows][768]
@@ -425,16 +350,9 @@ extern "C" int mdk_gru_create(const mdk_gru_desc *desc, const float *const *weig
     m->D = D;
     m->layers.resize(L);
     m->wide = H == kGH;
-    // process-wide defaults of the split scan (the options of the same names override them per model)
-    if (const char *e = getenv("MDK_SCAN_SPLIT")) m->opt_scan_split = std::min(std::max(atoi(e), 0), kMaxSplit);
-    if (const char *e = getenv("MDK_SCAN_SPLIT_ADAPT")) m->opt_split_adapt = std::max(atoi(e), 0);
-    if (const char *e = getenv("MDK_SCAN_SPLIT_PROBE")) m->opt_split_probe = atoi(e) ? 1 : 0;
+    m->policy.read_env();
     if (const char *e = getenv("MDK_EARLY_START")) m->opt_early_start = atoi(e) ? 1 : 0;
     if (const char *e = getenv("MDK_TAIL_BLIT")) m->opt_tail_blit = atoi(e) ? 1 : 0;
-    if (const char *e = getenv("MDK_SCAN_SPLIT_MARGIN")) {
-        const int g = atoi(e);
-        if (g >= 16 && g <= 4096 && g % 8 == 0) m->opt_split_margin = g;
-    }
     int rc = MDK_OK;
     auto bail = [&](int code) { mdk_gru_destroy(m); return code; };
     if ((rc = init_ctx(m))) return bail(rc);
@@ -656,23 +574,20 @@ extern "C" int mdk_gru_set_option(mdk_gru *m, const char *key, int value) {
         m->opt_gpu_share = value;
     } else if (!strcmp(key, "scan_split")) {
         if (value < 0 || value > kMaxSplit) return fail(MDK_ERR_ARG, "scan_split must be 0 (off), 1 (auto) or 2..%d chunks", kMaxSplit);
-        m->opt_scan_split = value;
-        m->split_disabled = false;           // setting the option re-arms a model that fell back
-        m->split_retry_in = m->split_backoff = 0;
-        m->margin.reset(true);
-        m->probed_ok.clear();
+        m->policy.opt_scan_split = value;
+        m->policy.rearm(true);
     } else if (!strcmp(key, "scan_split_audit")) {
         if (value < 0 || value > 2) return fail(MDK_ERR_ARG, "scan_split_audit must be 0, 1 or 2");
-        m->opt_split_audit = value;
+        m->policy.opt_split_audit = value;
     } else if (!strcmp(key, "scan_split_audit_every")) {
         if (value < 0) return fail(MDK_ERR_ARG, "scan_split_audit_every must be >= 0 (0 = only the first call of a margin)");
-        m->opt_split_audit_every = value;
+        m->policy.opt_split_audit_every = value;
     } else if (!strcmp(key, "scan_split_adapt")) {
         if (value < 0) return fail(MDK_ERR_ARG, "scan_split_adapt must be >= 0 (certified calls at the noise floor before a smaller margin is tried; 0 = never)");
-        m->opt_split_adapt = value;
-        m->margin.quiet = 0;
+        m->policy.opt_split_adapt = value;
+        m->policy.margin.quiet = 0;
     } else if (!strcmp(key, "scan_split_probe")) {
-        m->opt_split_probe = value ? 1 : 0;
+        m->policy.opt_split_probe = value ? 1 : 0;
     } else if (!strcmp(key, "async_depth")) {
         if (value < 1 || value > 64) return fail(MDK_ERR_ARG, "async_depth must be 1..64");
         m->opt_async_depth = value;              // (drop_pending above has retired every call in flight: the ring is resized by the next call)
@@ -681,10 +596,8 @@ extern "C" int mdk_gru_set_option(mdk_gru *m, const char *key, int value) {
         m->opt_wide_wait_ms = value;             // (gru_size 256: how long a cluster time-out is retried; no effect at 128)
     } else if (!strcmp(key, "scan_split_margin")) {
         if (value < 16 || value > 4096 || value % 8) return fail(MDK_ERR_ARG, "scan_split_margin must be a multiple of 8 in 16..4096");
-        m->opt_split_margin = value;
-        m->margin.reset(false);      // (what the certificates rejected so far stays learned: "scan_split" re-arms)
-        m->split_disabled = false;
-        m->split_retry_in = m->split_backoff = 0;
+        m->policy.opt_split_margin = value;
+        m->policy.rearm(false);
     } else {
         return fail(MDK_ERR_ARG, "unknown option '%s'", key);
     }
@@ -717,7 +630,7 @@ extern "C" int mdk_gru_get_split(mdk_gru *m, mdk_gru_split *out) {
         int rc = retire_async(m, true);
         if (rc) return rc;
     }
-    *out = m->last_split;
+    *out = m->policy.last_split;
     return MDK_OK;
 }
 extern "C" int mdk_gru_device(const mdk_gru *m) { return m ? m->device : -1; }

@@ -1,6 +1,7 @@
-// The split scan on the host side: shape arithmetic, enqueue / finish halves of a split call, the call-level state machine
-// (run_forward: certificate, margin learner, probe, audits, fallback) and the first attempt of a call started ahead (start_call).
-// Part of api.hip (included there after gru_pass.hpp).
+// The split scan on the host side: shape arithmetic, enqueue / finish halves of a split call, the two forwards that run it -- the
+// synchronous one (run_forward: wait, certificate, retries, audit, fallback) with the first attempt of a call started ahead
+// (start_call), and the stream-ordered one (enqueue_async, retire_one).  What a call's verdict teaches the model is SplitPolicy's
+// (split_policy.hpp), for both.  Part of api.hip (included there after gru_pass.hpp).
 #pragma once
 // ---- split scan (scan_split.hpp): plan, run on the virtual batch, certify, fall back
 // The shape arithmetic of a split, free of any model state (also exported as mdk_split_plan for hosts and CPU tests).
@@ -32,21 +33,21 @@ static bool plan_split_shape(int B, int T, int share, int mode, int G, size_t bu
 
 // The margin learner on a model that certifies iff the margin is >= `need` (0: never), with differences at the noise floor:
 // n_calls calls from `start`; margins[i] = the margin call i was ANSWERED at (0: sequentially), forwards[i] = split forwards
-// it cost (rejected ones included).  Device-free: the CPU tests drive the state machine through this.
+// it cost (rejected ones included).  Device-free: the CPU tests drive SplitPolicy's verdicts through this, as run_forward does
+// (fp32, auto mode); after a give-up every later call is answered sequentially (the back-off is not counted down here).
 extern "C" int mdk_margin_sim(int start, int adapt, int need, int n_calls, int *margins, int *forwards) {
     if (start < 16 || start > 4096 || adapt < 0 || need < 0 || n_calls < 0 || !margins || !forwards)
         return fail(MDK_ERR_ARG, "bad argument");
-    MarginLearner L;
-    bool disabled = false;
+    SplitPolicy P;
+    P.opt_scan_split = 1; P.opt_split_margin = start; P.opt_split_adapt = adapt;
     for (int i = 0; i < n_calls; ++i) {
         margins[i] = 0; forwards[i] = 0;
-        if (disabled) continue;
+        if (P.split_disabled) continue;
         for (;;) {
-            const int G = L.cur ? L.cur : start;
+            const int G = P.margin_in_use();
             forwards[i]++;
-            if (need > 0 && G >= need) { L.certified(G, 0.f, 1.f, adapt); margins[i] = G; break; }
-            int back = 0;
-            if (L.rejected(G, &back) == MarginLearner::GIVE_UP) { disabled = true; break; }
+            if (need > 0 && G >= need) { P.certified(G, MDK_PREC_FP32, true); margins[i] = G; break; }
+            if (!P.rejected(G, true)) break;
         }
     }
     return MDK_OK;
@@ -104,12 +105,12 @@ extern "C" int mdk_split_plan(int B, int T, int gpu_share, int scan_split, int m
 static bool plan_split(const mdk_gru *m, int B, int T, SplitPlan &p) {
     static const int env_abl = getenv("MDK_ABLATE") ? atoi(getenv("MDK_ABLATE")) : 0;
     p.S = 1;
-    if (m->opt_scan_split == 0 || (m->split_disabled && m->opt_scan_split == 1)) return false;
+    const SplitPolicy &P = m->policy;
+    if (P.opt_scan_split == 0 || (P.split_disabled && P.opt_scan_split == 1)) return false;
     if (m->wide) return false;             // GRU(256): sequential scans only
     if (m->variant != MDK_VARIANT_MFMA || m->D != 2 || m->desc.num_layers != 2 || m->opt_ablate || env_abl) return false;
     if (m->layers[0].K > 16) return false;
-    return plan_split_shape(B, T, m->opt_gpu_share, m->opt_scan_split, m->margin.cur ? m->margin.cur : m->opt_split_margin,
-                            m->max_rows_per_pass ? m->max_rows_per_pass : kMaxRowsPerPass, p);
+    return plan_split_shape(B, T, m->opt_gpu_share, P.opt_scan_split, P.margin_in_use(), m->max_rows_per_pass ? m->max_rows_per_pass : kMaxRowsPerPass, p);
 }
 
 // A split call in two halves, so that the staged entry can enqueue the NEXT batch's forward before it waits for this one's
@@ -214,9 +215,7 @@ static int split_finish(mdk_gru *m, const SplitPlan &sp, bool need_gi, EvTimer &
                     (y >> 1) & 1, y & 1, d);
         }
     }
-    m->last_split.chunks = sp.S; m->last_split.margin = sp.G; m->last_split.columns = sp.Tv;
-    m->last_split.max_delta = worst;
-    m->last_split.status = *certified ? MDK_SPLIT_CERTIFIED : MDK_SPLIT_REJECTED;
+    m->policy.record(sp.S, sp.G, sp.Tv, worst, *certified);
     return MDK_OK;
 }
 
@@ -229,12 +228,14 @@ static int run_split(mdk_gru *m, const SplitPlan &sp, const float *x_dev, float 
     return split_finish(m, sp, need_gi, tm, x_dev, probs_dev, s, probs_host, certified);
 }
 
-static void report_audits(mdk_gru *m) {
-    m->last_split.audits = (int)std::min<long>(m->audits_done, 0x7fffffff);
-    m->last_split.audit_failures = m->audit_failures;
-    m->last_split.audit_worst_dp = m->audit_worst;
-    m->last_split.probes = (int)std::min<long>(m->probes_done, 0x7fffffff);
-    m->last_split.probe_max_delta = m->probe_last_delta;
+// the buffer of an audit's sequential scan (n floats)
+static int ensure_audit(mdk_gru *m, size_t n) {
+    if (n > m->audit_cap) {
+        free_dev(m->audit); m->audit = nullptr; m->audit_cap = 0;
+        HIP_TRY(hipMalloc((void **)&m->audit, n * sizeof(float)));
+        m->audit_cap = n;
+    }
+    return MDK_OK;
 }
 
 // one call: split scan when the shape is latency-bound and the certificate holds, the sequential passes otherwise
@@ -247,14 +248,9 @@ static bool same_split(const SplitPlan &a, const SplitPlan &b) {
     return a.core0[a.S] == b.core0[b.S];
 }
 
-static bool split_probe_due(const mdk_gru *m, const SplitPlan &sp) {
-    return m->precision == MDK_PREC_FP16 && m->opt_scan_split == 1 && m->opt_split_probe &&
-           (std::find(m->probed_ok.begin(), m->probed_ok.end(), sp.G) == m->probed_ok.end() ||
-            (m->opt_split_audit == 1 && m->opt_split_audit_every > 0 && m->split_calls_since_audit + 1 >= m->opt_split_audit_every));
-}
-
 static int run_forward(mdk_gru *m, const float *x_dev, int B, int T, float *probs_dev, hipStream_t s,
                        const float *x_host, float *probs_host, mdk_gru::Started *pre = nullptr) {
+    SplitPolicy &P = m->policy;
     SplitPlan sp;
     int rc;
     bool first_attempt = true;
@@ -266,15 +262,7 @@ static int run_forward(mdk_gru *m, const float *x_dev, int B, int T, float *prob
         }
         return MDK_OK;
     };
-    const int fallbacks = m->last_split.fallbacks;
-    memset(&m->last_split, 0, sizeof(m->last_split));
-    m->last_split.chunks = 1; m->last_split.columns = T; m->last_split.fallbacks = fallbacks;
-    // A rejection at the largest margin may be the INPUT's doing (a zero-coverage run, a stretch the model was never
-    // trained on: dynamics that do not forget THERE), not the model's: the split is tried again after a back-off of
-    // 64, 128, ... 4096 calls, at the largest margin (one rejected forward per retry, < 1 % of the calls in between).
-    if (m->split_disabled && m->split_retry_in > 0 && --m->split_retry_in == 0) m->split_disabled = false;
-    m->last_split.status = m->split_disabled ? MDK_SPLIT_DISABLED : MDK_SPLIT_NOT_USED;
-    report_audits(m);
+    P.open_record(T, P.begin_call());
 #ifdef MDK_DEBUG_HOOKS
     static const bool keep = getenv("MDK_SPLIT_KEEP") != nullptr;   // debug builds only: deliver a rejected split as it is
 #else
@@ -289,7 +277,7 @@ static int run_forward(mdk_gru *m, const float *x_dev, int B, int T, float *prob
         // is used in half mode only after a call certified at it in FP32-PARITY mode: the call is run once more with the hi/lo
         // operands and the 2^-18 threshold (result discarded, x stays on the device), once per margin the learner visits and again
         // with every standing audit; a rejected probe is a rejected certificate (the margin climbs / the trial goes back).
-        const bool probe_due = split_probe_due(m, sp);
+        const bool probe_due = P.probe_due(sp.G, m->precision);
         const bool use_pre = first_attempt && pre && pre->valid && pre->split && pre->precision == m->precision && !probe_due &&
                              same_split(sp, pre->sp);
         if (first_attempt && !use_pre && (rc = forget_pre())) return rc;
@@ -302,11 +290,8 @@ static int run_forward(mdk_gru *m, const float *x_dev, int B, int T, float *prob
             m->precision = MDK_PREC_FP16;
             if (rc) return rc;
             x_host = nullptr;                     // x is on the device from here on
-            m->probes_done++;
-            m->probe_last_delta = m->last_split.max_delta;
-            m->probed_ok.erase(std::remove(m->probed_ok.begin(), m->probed_ok.end(), sp.G), m->probed_ok.end());
-            if (pok) m->probed_ok.push_back(sp.G);
-            else probe_rejected = true;
+            P.probed(sp.G, pok, P.last_split.max_delta);
+            probe_rejected = !pok;
         }
         if (!probe_rejected) {
             if (use_pre) {
@@ -319,121 +304,50 @@ static int run_forward(mdk_gru *m, const float *x_dev, int B, int T, float *prob
             }
             if (rc) return rc;
         }
-        report_audits(m);
         if (keep) return MDK_OK;
-        if (ok) {
-            m->split_backoff = 0;
-            // The margin is the split's price (12.8 % of all columns at 128, 5.7 % at 64) and what it has to be is the MODEL's
-            // forgetting length: after `scan_split_adapt` certified calls in a row whose largest junction difference sat at the
-            // rounding-noise floor (a quarter of the threshold), the next call tries one rung less.  A trial that is rejected
-            // costs that one forward: the call is repeated at the margin that worked, and no shrink goes below it again.
-            const float quiet_thr = 0.25f * (m->precision == MDK_PREC_FP16 ? kSplitEpsHalf : kSplitEps);
-            const int was = m->margin.certified(sp.G, m->last_split.max_delta, quiet_thr, m->opt_scan_split == 1 ? m->opt_split_adapt : 0);
-            if (was) fprintf(stderr, "[medaka_amd] split scan: certified at a margin of %d columns (was %d): kept\n", sp.G, was);
-            // Audit.  The certificate argues from the states at the junctions; the audit looks at what is delivered: the call is
-            // ALSO run as the sequential scan on the device and the two (B, T, C) results are compared in full.  Audited are the
-            // first certified call of a model (and the first at every margin / precision it moves to) and, as a STANDING check on
-            // whatever input the model meets later, every `scan_split_audit_every`-th certified call after that (default 256:
-            // one sequential forward of ~2x a split forward's time per 256 calls, < 1 %; a concurrent low-priority audit was
-            // tried first and cost far more -- any second tenant keeps the recurrence's work-groups from being resident
-            // together).  A mismatch delivers the sequential result and turns the split off for the model.
-            const int audit_key = sp.G | (m->precision << 16) | (1 << 24);
-            const bool first = m->split_audited_key != audit_key;
-            const bool periodic = !first && m->opt_split_audit_every > 0 && ++m->split_calls_since_audit >= m->opt_split_audit_every;
-            if (m->opt_split_audit == 0 || (m->opt_split_audit == 1 && !first && !periodic)) return MDK_OK;
-            m->split_calls_since_audit = 0;
-            const size_t n = (size_t)B * T * m->desc.num_classes;
-            if (n > m->audit_cap) {
-                free_dev(m->audit); m->audit = nullptr; m->audit_cap = 0;
-                HIP_TRY(hipMalloc((void **)&m->audit, n * sizeof(float)));
-                m->audit_cap = n;
-            }
-            const mdk_gru_split certified = m->last_split;
-            // (x_dev holds x also on the host path.)  The audit's scan is planned `lean`: it needs no gi -- 6 GB per buffer at
-            // 200 x 10 000, which an audit used to allocate and give back: memory handed back to the driver is wiped by the
-            // kernel ON THE DMA ENGINES, in the background, and while that ran (0.45 s for the two buffers) every strided copy of
-            // the host path took 130 us longer -- the "slow DMA state" of the first 40 calls after every audit, found in round 5
-            // (profiles/r5_experiments/README.md section 9).
-            rc = run_passes(m, x_dev, B, T, m->audit, s, nullptr, nullptr, /*lean=*/true);
-            if (rc) return rc;
-            if (!m->oor_seen) {             // (possibly) no gi, no device-side fallback: was x inside fp16 range?  (if not: once more, with it)
-                bool raised = false;
-                if ((rc = range_flag_raised(m, s, &raised))) return rc;
-                if (raised && (rc = run_passes(m, x_dev, B, T, m->audit, s, nullptr, nullptr))) return rc;
-            }
-            HIP_TRY(hipMemsetAsync(m->split_flag, 0, sizeof(unsigned), s));
-            hipLaunchKernelGGL(k_split_audit, dim3((unsigned)std::min<size_t>((n + 255) / 256, 256 * 8)), dim3(256), 0, s,
-                               (const float *)probs_dev, (const float *)m->audit, n, m->split_flag);
-            HIP_TRY(hipMemcpyAsync(m->split_host, m->split_flag, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            // (a shape whose sequential scan cannot run fused -- T not a multiple of the strip -- did allocate gi: it STAYS, the
-            // next audit of the shape needs it again and a hipFree of that size is 0.5 s of slow strided DMA, see above)
-            float dp;
-            memcpy(&dp, &m->split_host[0], sizeof(float));
-            m->audits_done++;
-            m->audit_worst = std::max(m->audit_worst, dp);
-            m->last_split = certified;
-            m->last_split.audited = 1;
-            m->last_split.audit_max_dp = dp;
-            if (dp <= (m->precision == MDK_PREC_FP16 ? kAuditTolHalf : kAuditTol)) {
-                m->split_audited_key = audit_key;
-                report_audits(m);
-                return MDK_OK;
-            }
-            // never seen: certified junctions, different probabilities.  The sequential result is already there.
-            fprintf(stderr, "[medaka_amd] split scan: an audit found |p_split - p_sequential| = %.3g behind a certified split (margin %d, "
-                            "%s call): the sequential result is delivered and the split scan is off for this model\n", dp, sp.G,
-                    first ? "first" : "a later");
-            m->audit_failures++;
-            m->last_split.status = MDK_SPLIT_REJECTED;
-            m->last_split.fallbacks++;
-            m->split_disabled = true;
-            report_audits(m);
-            HIP_TRY(hipMemcpyAsync(probs_dev, m->audit, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-            if (probs_host) HIP_TRY(hipMemcpyAsync(probs_host, m->audit, n * sizeof(float), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            return MDK_OK;
-        }
-        // Some junction did not merge: this model remembers further back than the margin.  Auto mode tries again with
-        // twice the margin and keeps it for later calls (said once on stderr).  A shape that no longer splits at the new
-        // margin is answered sequentially -- this call only; the model is given up (sequential scans from then on) only by
-        // a rejection AT kSplitMarginMax: a very long or chaotic memory.  A forced chunk count is not second-guessed: the
-        // call is answered sequentially.
-        m->last_split.fallbacks++;
-        m->margin.quiet = 0;
-        if (m->opt_scan_split != 1) break;
-        int was_trial = 0;
-        const MarginLearner::Next nx = m->margin.rejected(sp.G, &was_trial);
-        if (was_trial) {
-            // a shrink on trial did not certify: back to the margin that did (this call is repeated there)
-            fprintf(stderr, "[medaka_amd] split scan: a margin of %d columns does not certify (junction states differ by %.3g): back to %d\n",
-                    sp.G, m->last_split.max_delta, m->margin.cur);
-            continue;
-        }
-        const int next = m->margin.cur;
-        if (nx == MarginLearner::GIVE_UP) {
-            m->split_disabled = true;
-            m->split_backoff = m->split_backoff ? std::min<long>(2 * m->split_backoff, 4096) : 64;
-            m->split_retry_in = m->split_backoff;
-            if (m->split_backoff == 64)
-                fprintf(stderr, "[medaka_amd] split scan: junction states still differ by %.3g at a margin of %d columns: sequential scans "
-                                "for the next %ld calls, then another try (back-off doubling up to 4096 calls)\n",
-                        m->last_split.max_delta, sp.G, m->split_backoff);
+        if (!ok) {
+            if (P.rejected(sp.G, true)) continue;
             break;
         }
-        fprintf(stderr, "[medaka_amd] split scan: junction states differed by %.3g at a margin of %d columns: margin %d from now on\n",
-                m->last_split.max_delta, sp.G, next);
+        P.certified(sp.G, m->precision, true);
+        if (!P.audit_due(sp.G, m->precision)) return MDK_OK;
+        const size_t n = (size_t)B * T * m->desc.num_classes;
+        if ((rc = ensure_audit(m, n))) return rc;
+        // (x_dev holds x also on the host path.)  The audit's scan is planned `lean`: it needs no gi -- 6 GB per buffer at
+        // 200 x 10 000, which an audit used to allocate and give back: memory handed back to the driver is wiped by the
+        // kernel ON THE DMA ENGINES, in the background, and while that ran (0.45 s for the two buffers) every strided copy of
+        // the host path took 130 us longer -- the "slow DMA state" of the first 40 calls after every audit, found in round 5
+        // (profiles/r5_experiments/README.md section 9).
+        rc = run_passes(m, x_dev, B, T, m->audit, s, nullptr, nullptr, /*lean=*/true);
+        if (rc) return rc;
+        if (!m->oor_seen) {             // (possibly) no gi, no device-side fallback: was x inside fp16 range?  (if not: once more, with it)
+            bool raised = false;
+            if ((rc = range_flag_raised(m, s, &raised))) return rc;
+            if (raised && (rc = run_passes(m, x_dev, B, T, m->audit, s, nullptr, nullptr))) return rc;
+        }
+        HIP_TRY(hipMemsetAsync(m->split_flag, 0, sizeof(unsigned), s));
+        hipLaunchKernelGGL(k_split_audit, dim3((unsigned)std::min<size_t>((n + 255) / 256, 256 * 8)), dim3(256), 0, s,
+                           (const float *)probs_dev, (const float *)m->audit, n, m->split_flag);
+        HIP_TRY(hipMemcpyAsync(m->split_host, m->split_flag, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        // (a shape whose sequential scan cannot run fused -- T not a multiple of the strip -- did allocate gi: it STAYS, the
+        // next audit of the shape needs it again and a hipFree of that size is 0.5 s of slow strided DMA, see above)
+        float dp;
+        memcpy(&dp, &m->split_host[0], sizeof(float));
+        if (P.audit_passed(sp.G, m->precision, dp)) return MDK_OK;
+        // the sequential result is already there
+        HIP_TRY(hipMemcpyAsync(probs_dev, m->audit, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (probs_host) HIP_TRY(hipMemcpyAsync(probs_host, m->audit, n * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return MDK_OK;
     }
     if (first_attempt && pre && pre->valid && !pre->split && pre->precision == m->precision) {
         pre->valid = false;            // the sequential passes are what start_call enqueued: the caller's synchronize ends them
         m->early_used++;
-        report_audits(m);
         return MDK_OK;
     }
     if ((rc = forget_pre())) return rc;
-    rc = run_passes(m, x_dev, B, T, probs_dev, s, x_host, probs_host);
-    report_audits(m);
-    return rc;
+    return run_passes(m, x_dev, B, T, probs_dev, s, x_host, probs_host);
 }
 
 // The first attempt of a call, enqueue only: what run_forward would launch for (x_dev, B, T) right now -- a split scan at the
@@ -449,9 +363,9 @@ static int start_call(mdk_gru *m, const float *x_dev, int B, int T, float *probs
     int rc;
     // (the back-off of a model whose certificate was rejected at the largest margin counts calls in run_forward: a call that
     // would end it is left to run_forward)
-    if (m->split_disabled && m->split_retry_in == 1) return MDK_OK;
+    if (m->policy.backoff_ends_next_call()) return MDK_OK;
     const bool split = plan_split(m, B, T, sp);
-    if (split && split_probe_due(m, sp)) return MDK_OK;
+    if (split && m->policy.probe_due(sp.G, m->precision)) return MDK_OK;
     const size_t budget = m->max_rows_per_pass ? m->max_rows_per_pass : kMaxRowsPerPass;
     if (!split && (size_t)B * T > budget) return MDK_OK;
     int wgs = 256;
@@ -500,87 +414,23 @@ static int start_call(mdk_gru *m, const float *x_dev, int B, int T, float *probs
 // when its gate is closed.  What run_forward learns from a call (margin learner, back-off, probe and audit counters, last_split) is
 // learned when the call's record is retired: it is copied to a page-locked ring slot behind the call, and read once its event is done.
 
-// feed the host's bookkeeping from one retired call -- what run_forward does after its wait, in the same order
+// one retired call: its verdict goes to the policy, as run_forward's does after its wait, with the epoch, precision and margin
+// the call was enqueued with
 static void retire_one(mdk_gru *m, const mdk_gru::AsyncSlot &sl, const AsyncRecord &r) {
-    const int fallbacks = m->last_split.fallbacks;
-    memset(&m->last_split, 0, sizeof(m->last_split));
-    m->last_split.chunks = 1; m->last_split.columns = sl.T; m->last_split.fallbacks = fallbacks;
-    m->last_split.status = sl.status;
-    if (!sl.split) { report_audits(m); return; }
-    m->last_split.chunks = sl.S; m->last_split.margin = sl.G; m->last_split.columns = sl.Tv;
-    m->last_split.max_delta = r.worst;
-    if (sl.probe_ran) {
-        m->probes_done++;
-        m->probe_last_delta = r.probe_delta;
-        m->probed_ok.erase(std::remove(m->probed_ok.begin(), m->probed_ok.end(), sl.G), m->probed_ok.end());
-        if (r.probe_ok) m->probed_ok.push_back(sl.G);
-        if (m->probe_inflight_G == sl.G) m->probe_inflight_G = 0;
-        if (!r.probe_ok) m->last_split.max_delta = r.probe_delta;      // (as run_forward: a rejected probe is the call's certificate)
-    }
-    if (sl.audited && m->audit_inflight_key == sl.audit_key) m->audit_inflight_key = 0;
-    // Calls enqueued before an earlier one's verdict was retired were planned under a learner state that verdict has since changed
-    // (a margin, a trial, the back-off): only a call of the current EPOCH -- enqueued after the last retirement that moved the learner
-    // or the back-off -- moves them.  So one episode of rejections moves the learner one step and starts ONE back-off, as in
-    // run_forward, however many calls were in flight (at the largest margin GIVE_UP leaves the margin where it was: without the epoch
-    // every call in flight would double the back-off again).
-    const bool current = sl.epoch == m->learner_epoch && sl.precision == m->precision &&
-                         (m->margin.cur ? m->margin.cur : m->opt_split_margin) == sl.G;
-    if (r.certified) {
-        m->last_split.status = MDK_SPLIT_CERTIFIED;
-        if (current) {
-            m->split_backoff = 0;
-            const int cur0 = m->margin.cur, trial0 = m->margin.trial_back;
-            const float quiet_thr = 0.25f * (sl.precision == MDK_PREC_FP16 ? kSplitEpsHalf : kSplitEps);
-            const int was = m->margin.certified(sl.G, r.worst, quiet_thr, m->opt_scan_split == 1 ? m->opt_split_adapt : 0);
-            if (was) fprintf(stderr, "[medaka_amd] split scan: certified at a margin of %d columns (was %d): kept\n", sl.G, was);
-            if (m->margin.cur != cur0 || m->margin.trial_back != trial0) m->learner_epoch++;
-        }
-        if (sl.audited) {
-            float dp;
-            memcpy(&dp, &r.audit_bits, sizeof(float));
-            m->audits_done++;
-            m->audit_worst = std::max(m->audit_worst, dp);
-            m->last_split.audited = 1;
-            m->last_split.audit_max_dp = dp;
-            if (dp <= (sl.precision == MDK_PREC_FP16 ? kAuditTolHalf : kAuditTol)) {
-                m->split_audited_key = sl.audit_key;
-            } else {
-                fprintf(stderr, "[medaka_amd] split scan: an audit found |p_split - p_sequential| = %.3g behind a certified split (margin %d): "
-                                "the sequential result was delivered and the split scan is off for this model\n", dp, sl.G);
-                m->audit_failures++;
-                m->last_split.status = MDK_SPLIT_REJECTED;
-                m->last_split.fallbacks++;
-                m->split_disabled = true;
-                m->learner_epoch++;
-            }
-        }
-        report_audits(m);
-        return;
-    }
+    SplitPolicy &P = m->policy;
+    P.open_record(sl.T, sl.status);
+    if (!sl.split) return;
+    P.record(sl.S, sl.G, sl.Tv, r.worst, r.certified);
+    if (sl.probe_ran) P.probed(sl.G, r.probe_ok, r.probe_delta);
+    if (sl.audited && P.audit_inflight_key == sl.audit_key) P.audit_inflight_key = 0;
+    const bool current = P.is_current(sl.epoch, sl.precision, sl.G, m->precision);
     // rejected: the sequential scan was delivered.  The learner takes one step; the next call ENQUEUED after this point uses it.
-    m->last_split.status = MDK_SPLIT_REJECTED;
-    m->last_split.fallbacks++;
-    report_audits(m);
-    if (!current) return;
-    m->margin.quiet = 0;
-    if (m->opt_scan_split != 1) return;
-    int was_trial = 0;
-    const MarginLearner::Next nx = m->margin.rejected(sl.G, &was_trial);
-    m->learner_epoch++;
-    if (was_trial) {
-        fprintf(stderr, "[medaka_amd] split scan: a margin of %d columns does not certify (junction states differ by %.3g): back to %d\n",
-                sl.G, m->last_split.max_delta, m->margin.cur);
-    } else if (nx == MarginLearner::GIVE_UP) {
-        m->split_disabled = true;
-        m->split_backoff = m->split_backoff ? std::min<long>(2 * m->split_backoff, 4096) : 64;
-        m->split_retry_in = m->split_backoff;
-        if (m->split_backoff == 64)
-            fprintf(stderr, "[medaka_amd] split scan: junction states still differ by %.3g at a margin of %d columns: sequential scans "
-                            "for the next %ld calls, then another try (back-off doubling up to 4096 calls)\n",
-                    m->last_split.max_delta, sl.G, m->split_backoff);
-    } else {
-        fprintf(stderr, "[medaka_amd] split scan: junction states differed by %.3g at a margin of %d columns: margin %d from now on\n",
-                m->last_split.max_delta, sl.G, m->margin.cur);
+    if (!r.certified) { (void)P.rejected(sl.G, current); return; }
+    P.certified(sl.G, sl.precision, current);
+    if (sl.audited) {
+        float dp;
+        memcpy(&dp, &r.audit_bits, sizeof(float));
+        (void)P.audit_passed(sl.G, sl.precision, dp);      // (a failed audit: k_audit_deliver has delivered the sequential result)
     }
 }
 
@@ -608,7 +458,7 @@ static void free_async(mdk_gru *m) {
     m->async_host = nullptr;
     free_dev(reinterpret_cast<float *>(m->async_dev)); m->async_dev = nullptr;
     free_dev(reinterpret_cast<float *>(m->probe_flag)); m->probe_flag = nullptr;
-    m->probe_inflight_G = m->audit_inflight_key = 0;
+    m->policy.probe_inflight_G = m->policy.audit_inflight_key = 0;
 }
 
 // the device words and a ring of "async_depth" slots (a new depth: every call in flight is retired first -- a wait, once)
@@ -642,9 +492,9 @@ static int enqueue_async_body(mdk_gru *m, const float *x_dev, int B, int T, floa
     // the workspace is the model's: this call's stream waits (on the device) for the previous call, whatever stream that was on
     if (m->async_last) HIP_TRY(hipStreamWaitEvent(s, m->async_last, 0));
     // the back-off counts calls, as in run_forward -- here calls enqueued
-    if (m->split_disabled && m->split_retry_in > 0 && --m->split_retry_in == 0) { m->split_disabled = false; m->learner_epoch++; }
-    sl.epoch = m->learner_epoch;
-    sl.status = m->split_disabled ? MDK_SPLIT_DISABLED : MDK_SPLIT_NOT_USED;
+    SplitPolicy &P = m->policy;
+    sl.status = P.begin_call();
+    sl.epoch = P.learner_epoch;
     SplitPlan sp;
     int rc;
     if (!plan_split(m, B, T, sp)) {
@@ -660,10 +510,8 @@ static int enqueue_async_body(mdk_gru *m, const float *x_dev, int B, int T, floa
         //    which the split below overwrites in full (as in run_forward).  A probe of this margin still in flight from an earlier
         //    call is not repeated: this call is gated on that probe's verdict, which stays in the device words.
         int probe = 0;
-        if (split_probe_due(m, sp)) {
-            const bool periodic = m->opt_split_audit == 1 && m->opt_split_audit_every > 0 &&
-                                  m->split_calls_since_audit + 1 >= m->opt_split_audit_every;
-            if (!periodic && m->probe_inflight_G == sp.G) {
+        if (P.probe_due(sp.G, m->precision)) {
+            if (!P.periodic_audit_next() && P.probe_inflight_G == sp.G) {
                 probe = 2;
             } else {
                 m->precision = MDK_PREC_FP32;
@@ -672,7 +520,7 @@ static int enqueue_async_body(mdk_gru *m, const float *x_dev, int B, int T, floa
                 if (rc) return rc;
                 probe = 1;
                 sl.probe_ran = true;
-                m->probe_inflight_G = sp.G;
+                P.probe_inflight_G = sp.G;
             }
         }
         // 2. the split at the margin in use, its certificate into split_flag
@@ -687,17 +535,9 @@ static int enqueue_async_body(mdk_gru *m, const float *x_dev, int B, int T, floa
         // 5. the audit (the first call at a margin / precision, then every "scan_split_audit_every"-th split call ENQUEUED): the
         //    sequential scan into m->audit, predicated on "certified", compared in full; where it differs by more than the
         //    tolerance its result is copied over the split's by a predicated kernel
-        const int audit_key = sp.G | (m->precision << 16) | (1 << 24);
-        const bool first = m->split_audited_key != audit_key && m->audit_inflight_key != audit_key;
-        const bool periodic = !first && m->opt_split_audit_every > 0 && ++m->split_calls_since_audit >= m->opt_split_audit_every;
-        if (m->opt_split_audit == 2 || (m->opt_split_audit == 1 && (first || periodic))) {
-            m->split_calls_since_audit = 0;
+        if (const int audit_key = P.audit_due(sp.G, m->precision)) {
             const size_t n = (size_t)B * T * m->desc.num_classes;
-            if (n > m->audit_cap) {
-                free_dev(m->audit); m->audit = nullptr; m->audit_cap = 0;
-                HIP_TRY(hipMalloc((void **)&m->audit, n * sizeof(float)));
-                m->audit_cap = n;
-            }
+            if ((rc = ensure_audit(m, n))) return rc;
             if ((rc = run_passes(m, x_dev, B, T, m->audit, s, nullptr, nullptr, /*lean=*/true, &w->gate[1]))) return rc;
             const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 256 * 8);
             hipLaunchKernelGGL(k_split_audit, dim3(blocks), dim3(256), 0, s, (const float *)probs_dev, (const float *)m->audit, n,
@@ -707,7 +547,7 @@ static int enqueue_async_body(mdk_gru *m, const float *x_dev, int B, int T, floa
                                m->precision == MDK_PREC_FP16 ? kAuditTolHalf : kAuditTol);
             sl.audited = true;
             sl.audit_key = audit_key;
-            m->audit_inflight_key = audit_key;
+            P.audit_inflight_key = audit_key;
         }
         // 6. the record goes home
         HIP_TRY(hipMemcpyAsync(&m->async_host[idx], &w->rec, sizeof(AsyncRecord), hipMemcpyDeviceToHost, s));
@@ -721,16 +561,11 @@ static int enqueue_async_body(mdk_gru *m, const float *x_dev, int B, int T, floa
 }
 
 // one call, enqueued on `s`; the caller has dropped a batch started ahead, checked the arguments and made room in the ring.  A call
-// that fails part way leaves the bookkeeping as it found it: no slot will ever retire what it would have advanced (an in-flight
-// probe later calls would be gated on, an audit, the cadence and back-off counters)
+// that fails part way leaves the policy as it found it: no slot will ever retire what it would have advanced (an in-flight probe
+// later calls would be gated on, an audit, the cadence and back-off counters)
 static int enqueue_async(mdk_gru *m, const float *x_dev, int B, int T, float *probs_dev, hipStream_t s) {
-    const bool disabled = m->split_disabled;
-    const long retry_in = m->split_retry_in, since_audit = m->split_calls_since_audit, epoch = m->learner_epoch;
-    const int probe_G = m->probe_inflight_G, audit_key = m->audit_inflight_key;
+    const SplitPolicy before = m->policy;
     const int rc = enqueue_async_body(m, x_dev, B, T, probs_dev, s);
-    if (rc) {
-        m->split_disabled = disabled; m->split_retry_in = retry_in; m->split_calls_since_audit = since_audit; m->learner_epoch = epoch;
-        m->probe_inflight_G = probe_G; m->audit_inflight_key = audit_key;
-    }
+    if (rc) m->policy = before;
     return rc;
 }

@@ -26,7 +26,7 @@
 
 namespace mdk {
 
-constexpr int kSplitMarginMax = 512;      // auto mode climbs a ladder of margins up to here (api.hip kMarginLadder), then gives the model up
+constexpr int kSplitMarginMax = 512;      // auto mode climbs a ladder of margins up to here (split_policy.hpp kMarginLadder), then gives the model up
 constexpr int kSplitFlagWords = 8 * (kMaxSplit - 1);   // certificate words on the device: one per certificate point
 // Largest junction difference that certifies, on h in [-1, 1].  Two scans that have merged still differ by the rounding
 // noise of their different histories, and how large that is depends on the MODEL (its gains amplify the 2^-22 of the fp16

@@ -117,7 +117,7 @@ def test_premise_on_the_reference_arithmetic(gold):
             assert d > 1e-2, (name, scale, d)
 
 
-# ---- the margin learner (api.hip MarginLearner, exported device-free as mdk_margin_sim) -----------------------------------
+# ---- the margin learner (split_policy.hpp SplitPolicy, exported device-free as mdk_margin_sim) -----------------------------
 LADDER = (64, 96, 128, 192, 256, 384, 512)
 
 

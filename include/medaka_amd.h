@@ -246,6 +246,24 @@ int mdk_gru_set_normalise(mdk_gru *m, int normalise);
  *                                                   of h (threshold 2^-10) and cannot see an un-merged state below ~1e-3; without
  *                                                   the probe its learner shrinks to margins fp32 parity rejects for the same
  *                                                   weights.  0: trust the half certificate alone (environment MDK_SCAN_SPLIT_PROBE)
+ *   "scan_split_trim"      = 1 | 0 | 2              what the LAST layer scans of a chunk (the first layer always scans core + margin on
+ *                                                   either side).  Behind its core, in scan order, the last layer's state is read only by
+ *                                                   the certificate's second point, margin / 2 columns past the junction; before its core
+ *                                                   its first margin / 2 columns are fed by a first layer that is itself still warming up.
+ *                                                   1 (default): the trailing margin / 2 columns are not scanned.  Nothing reads them, so
+ *                                                   interior chunks compute the bits of 0, the whole virtual window; the two edge chunks
+ *                                                   (whose windows carry 2 * margin of lead) warm up over margin columns like every
+ *                                                   other junction.  Where the certificate holds the trajectories have merged: measured
+ *                                                   on seven weight sets, certified calls deliver the same bits and the same
+ *                                                   mdk_gru_get_split record as 0 -- an observation, not a guarantee; a REJECTED call's
+ *                                                   max_delta can differ in its last digits (its answer is the sequential scan's either way).
+ *                                                   2: nor the leading margin / 2 -- core + margin columns per direction instead of
+ *                                                   core + 2 * margin; results differ from 0 at the rounding-noise level, as results at
+ *                                                   two margins do, the certificate is unchanged and decides, as ever, whether the margin
+ *                                                   is enough: a model with a long memory may need the next larger one (why 2 is not
+ *                                                   the default).  Takes effect where the last layer's scan writes the probabilities
+ *                                                   itself ("final_head"); mdk_split_scan_ranges gives the ranges
+ *                                                   (environment MDK_SCAN_SPLIT_TRIM)
  *   "scan_split_audit"     = 1 | 0 | 2              1: the first certified call of a model -- and the first at every margin
  *                                                   it escalates to, and every "scan_split_audit_every"-th after that -- is
  *                                                   also run as the sequential scan and the two
@@ -302,6 +320,22 @@ typedef struct {
     int start[16], first[16], last[16];
 } mdk_split_shape;
 int mdk_split_plan(int B, int T, int gpu_share, int scan_split, int margin, mdk_split_shape *out);
+/* What the LAST layer of a split call scans inside every chunk (option "scan_split_trim" = `trim`; device-free, the other arguments as
+ * for mdk_split_plan, whose output this does not change).  Local columns of chunk k's virtual window (add start[k] for real ones),
+ * multiples of 8: the forward scan runs [lo_fwd[k], hi_fwd[k]) upwards, the reverse scan [lo_rev[k], hi_rev[k]) downwards, in two
+ * launches that meet at mid[k]: forward [lo_fwd, mid) with reverse [mid, hi_rev), then forward [mid, hi_fwd) with reverse
+ * [lo_rev, mid).  (A recurrence tile whose 8 windows belong to two chunks runs the union of their ranges.) */
+typedef struct {
+    int chunks, trim;
+    int lo_fwd[16], hi_fwd[16], lo_rev[16], hi_rev[16], mid[16];
+} mdk_split_ranges;
+int mdk_split_scan_ranges(int B, int T, int gpu_share, int scan_split, int margin, int trim, mdk_split_ranges *out);
+/* ... and what the device runs: the recurrence works on tiles of 8 consecutive virtual windows (virtual window k * B + w is chunk k
+ * of window w), and a tile takes the union of the ranges of the chunks its windows belong to and the midpoint of that union.
+ * *n_tiles = tiles of the virtual batch; out[5 * t .. 5 * t + 4] = lo_fwd, hi_fwd, lo_rev, hi_rev, mid of tile t, for the first
+ * min(*n_tiles, max_tiles) tiles (max_tiles = 0: only count).  A launch lasts as long as its longest tile: the first half
+ * max(mid - lo_fwd, hi_rev - mid) steps, the second max(hi_fwd - mid, mid - lo_rev). */
+int mdk_split_tile_ranges(int B, int T, int gpu_share, int scan_split, int margin, int trim, int max_tiles, int *n_tiles, int *out);
 /* The margin learner (option "scan_split_adapt") on a model that certifies iff the margin is >= `need` (0: never): n_calls calls
  * from margin `start`; margins[i] = the margin call i was answered at (0: sequentially), forwards[i] = the split forwards it cost.
  * Device-free, for tests and for reasoning about what a model with a known forgetting length will pay. */

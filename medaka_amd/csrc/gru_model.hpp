@@ -73,6 +73,9 @@ struct mdk_gru : Ctx {
     int opt_ablate = 0;         // timing-only ablation mask of the recurrence kernel
     size_t max_rows_per_pass = 0;   // 0 = kMaxRowsPerPass
     int opt_fuse_l0 = 1;        // fuse the layer-0 input projection into the recurrence
+    int opt_split_trim = 1;     // split scan: what the last layer scans of a chunk (gru_split.hpp plan_scan_ranges): 0 the whole virtual window,
+                                // 1 without the trailing outer half-margin (same bits), 2 without the leading one as well (`hp` then
+                                // needs a margin of 256 instead of 192: DESIGN.md section 4.9)
     int opt_final_head = 1;     // fused head: the scan's second half writes probabilities itself (rec_fused.hpp HEAD = 2); 0: k_head_combine
     int opt_fuse_head = 1;      // last layer with a fused projection: Linear(D*128 -> 5) inside the recurrence kernel too (rec_fused.hpp HEAD)
     half8 *wlin_frag = nullptr; // [D][4 ksteps][2 hi/lo][64 lanes] B-fragments of linear.weight (classes padded to 16 columns)
@@ -506,6 +509,7 @@ extern "C" int mdk_gru_create(const mdk_gru_desc *desc, const float *const *weig
     if (const char *e = getenv("MDK_FUSE_HEAD")) m->opt_fuse_head = atoi(e) ? 1 : 0;
     if (const char *e = getenv("MDK_FINAL_HEAD")) m->opt_final_head = atoi(e) ? 1 : 0;
     if (const char *e = getenv("MDK_FUSE_PROJ")) m->opt_fuse_proj = std::min(std::max(atoi(e), 0), 2);
+    if (const char *e = getenv("MDK_SCAN_SPLIT_TRIM")) m->opt_split_trim = std::min(std::max(atoi(e), 0), 2);
 
     *out = m;
     return MDK_OK;
@@ -586,6 +590,9 @@ extern "C" int mdk_gru_set_option(mdk_gru *m, const char *key, int value) {
         if (value < 0) return fail(MDK_ERR_ARG, "scan_split_adapt must be >= 0 (certified calls at the noise floor before a smaller margin is tried; 0 = never)");
         m->policy.opt_split_adapt = value;
         m->policy.margin.quiet = 0;
+    } else if (!strcmp(key, "scan_split_trim")) {
+        if (value < 0 || value > 2) return fail(MDK_ERR_ARG, "scan_split_trim must be 0 (whole window), 1 (trailing trim) or 2 (trailing and leading trim)");
+        m->opt_split_trim = value;
     } else if (!strcmp(key, "scan_split_probe")) {
         m->policy.opt_split_probe = value ? 1 : 0;
     } else if (!strcmp(key, "async_depth")) {

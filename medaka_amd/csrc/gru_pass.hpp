@@ -229,7 +229,7 @@ struct Pass {
                                              // after its certificate kernel) instead of a wait on `s`
     const int *gate;                         // predicated pass (the stream-ordered entry's repair and audit): every kernel of the
                                              // pass returns at once while *gate != 0 (common.hpp gated_off); null = always runs
-    struct OutRange { hipEvent_t ready; int t0, nt; int launch; };
+    struct OutRange { hipEvent_t ready; int t0, nt; int launch; int chunk; };   // chunk: split calls only (local columns of that chunk)
     std::vector<OutRange> out_ranges;        // column ranges to copy out; issued after every launch is enqueued, because a
                                              // copy into pageable memory may block the calling thread until it is done
     const float *in = nullptr;               // input of the current layer
@@ -242,6 +242,7 @@ struct Pass {
     int run_exact();
     int layer(int l);
     int layer_final_head(int l, const LayerDev &Ld, float *outp);
+    int layer_final_head_ranged(int l, const LayerDev &Ld, float *outp);
     int layer_phased(int l, const LayerDev &Ld, float *outp, bool fuse, bool slabs, bool dev_slabs, bool side_gemm, bool side_head);
     int copy_out();
     // launches
@@ -251,7 +252,8 @@ struct Pass {
     void pack_cols(const LayerDev &Lp, const float *src, int t0, int nt, hipStream_t st);
     int copy_in_cols(int t0, int nt);
     void launch_gi_small(int l, const LayerDev &Ld, const int *cond);
-    void launch_rec(int l, const LayerDev &Ld, const float *gi_src, float *outp, bool xin, const int *cnd, int want, int rs0, int rns, bool fin = false);
+    void launch_rec(int l, const LayerDev &Ld, const float *gi_src, float *outp, bool xin, const int *cnd, int want, int rs0, int rns, bool fin = false,
+                    int rng = 0);
     void launch_rec_fallback(const LayerDev &Ld, const float *gi_src, float *outp, const int *cnd, int rs0, int rns);
 #ifdef MDK_DEBUG_HOOKS
     int launch_rec_ablated(const LayerDev &Ld, const float *gi_src, float *outp, int rs0, int rns);
@@ -350,14 +352,17 @@ void Pass::launch_gi_small(int l, const LayerDev &Ld, const int *cond) {
 // one recurrence launch over the scan steps [rs0, rs0 + rns) of layer l.
 // `fin`: this launch's columns are complete (second half of a bidirectional scan, any step of a one-directional
 // one): the fused head writes probabilities instead of partial logits (rec_fused.hpp HEAD = 2)
-void Pass::launch_rec(int l, const LayerDev &Ld, const float *gi_src, float *outp, bool xin, const int *cnd, int want, int rs0, int rns, bool fin) {
+// `rng` (split scan, last layer with the fused head): every work-group takes its steps from the plan's scan ranges -- 1 the
+// first half, 2 a launch of the second: `rns` columns from `rs0` columns past the midpoint (rec_fused.hpp)
+void Pass::launch_rec(int l, const LayerDev &Ld, const float *gi_src, float *outp, bool xin, const int *cnd, int want, int rs0, int rns, bool fin,
+                      int rng) {
     const int nq = P.nq, D = P.D, L = P.L;
     if (l >= 1 && P.fuse_proj) {
         const int hd = (P.fuse_head && l == L - 1) ? (fin ? 2 : 1) : 0;
 #define MDK_LAUNCH_FUSED(KS, HD, HPF)                                                                                         \
     hipLaunchKernelGGL((k_rec_fused<KS, HD, HPF>), rgrid(), dim3(512), fused_lds_bytes(KS, HPF), s, in, Ld.wih_frag, Ld.bias_gi, \
                        Ld.whh_frag, Ld.b_hn, outp, P.n_tiles, P.T, D, Ld.inv_scale_rec, Ld.inv_scale_gi, Ld.up_scale_rec,   \
-                       kActScale, reverse_mask(), rs0, rns, (const half8 *)m->wlin_frag, m->lin_inv_scale, m->lpart,        \
+                       kActScale, reverse_mask(), rs0, rns, (rng ? rng == 1 : rs0 == 0) ? 1 : 0, rng, (const half8 *)m->wlin_frag, m->lin_inv_scale, m->lpart,        \
                        (const float *)m->lin_b, probs, P.nb, (int)m->desc.normalise, sp ? *sp : SplitPlan{}, gate)
 #define MDK_LAUNCH_FUSED_P(KS, HD) do { if (P.hp) MDK_LAUNCH_FUSED(KS, HD, true); else MDK_LAUNCH_FUSED(KS, HD, false); } while (0)
 #define MDK_LAUNCH_FUSED_H(KS) do { if (hd == 2) MDK_LAUNCH_FUSED_P(KS, 2); else if (hd == 1) MDK_LAUNCH_FUSED_P(KS, 1); else MDK_LAUNCH_FUSED_P(KS, 0); } while (0)
@@ -460,20 +465,17 @@ int Pass::run_exact() {
 int Pass::layer_final_head(int l, const LayerDev &Ld, float *outp) {
     const int T = P.T, D = P.D;
     int rc;
+    if (sp && D == 2) return layer_final_head_ranged(l, Ld, outp);
     std::vector<int> ph{0};
     if (D == 2) {
         ph.push_back(T / 2);
         // (a launch's columns must have crossed PCIe before the next launch ends: ~0.9 us per column pair of a
-        // 200-window batch + ~10 us per copy against 1.8 us per step -- halvings keep that.  A split scan's LAST launch
-        // is its outer margin, [T - G, T): only the two edge chunks deliver anything from it -- the first and last G
-        // columns of every window, two copies -- so all but those have left when the scan ends.)
+        // 200-window batch + ~10 us per copy against 1.8 us per step -- halvings keep that)
         if (P.stream_out) {
-            const int last_cut = sp ? T - sp->G : T;
-            for (int k = 1; k <= (sp ? 3 : 4); ++k) {
+            for (int k = 1; k <= 4; ++k) {
                 const int cut = T / 2 + ((T / 2) - ((T / 2) >> k)) / kFusedSteps * kFusedSteps;
-                if (cut > ph.back() && cut < T && (!sp || cut + 64 < last_cut)) ph.push_back(cut);
+                if (cut > ph.back() && cut < T) ph.push_back(cut);
             }
-            if (sp && last_cut > ph.back() && last_cut % kFusedSteps == 0) ph.push_back(last_cut);
         }
     }
     ph.push_back(T);
@@ -486,10 +488,66 @@ int Pass::layer_final_head(int l, const LayerDev &Ld, float *outp) {
         if ((rc = pool_event(m, &ev))) return rc;
         HIP_TRY(hipEventRecord(ev, s));
         const int lo0 = T - ph[p + 1], hi0 = ph[p], len = ph[p + 1] - ph[p];
-        if (lo0 + len == hi0) out_ranges.push_back({ev, lo0, 2 * len, (int)p});
-        else { out_ranges.push_back({ev, lo0, len, (int)p}); out_ranges.push_back({ev, hi0, len, (int)p}); }
+        if (lo0 + len == hi0) out_ranges.push_back({ev, lo0, 2 * len, (int)p, 0});
+        else { out_ranges.push_back({ev, lo0, len, (int)p, 0}); out_ranges.push_back({ev, hi0, len, (int)p, 0}); }
     }
     m->last.rec_launches--;   // (the caller counts the layer once)
+    head_done = true;
+    return MDK_OK;
+}
+
+// ... of a split scan: every work-group scans the range the plan gives its tile (layout.hpp split_tile_range; option
+// "scan_split_trim", gru_split.hpp plan_scan_ranges) in two halves that meet at the tile's midpoint.  The launches are laid out
+// in columns PAST THE MIDPOINT in scan order: the first half is one launch, the second [0, H) with H the longest half of any
+// tile -- a launch lasts as long as its longest tile -- cut again on the host path.  After the launch that ends `b` columns past
+// the midpoints, chunk k has finished, for all its windows, the local columns [max(lo_r, mid - b), min(hi_f, mid + b)) of every
+// tile it has windows in: what is new of their intersection crosses PCIe under the next launch.
+int Pass::layer_final_head_ranged(int l, const LayerDev &Ld, float *outp) {
+    int rc;
+    int H = 0;
+    for (int t = 0; t < P.n_tiles; ++t) {
+        const ScanRange r = split_tile_range(*sp, t, P.nb);
+        H = std::max({H, r.hi_f - r.mid, r.mid - r.lo_r});
+    }
+    std::vector<int> off{0};
+    if (P.stream_out) {
+        // (a launch's columns must have crossed PCIe before the next launch ends: halvings keep that.  The LAST launch is the
+        // part of the range behind the cores -- the columns up to the certificate's second point, or the whole outer margin of
+        // an untrimmed scan: only the two edge chunks deliver anything from it, so all but that has left when the scan ends.)
+        const int last_cut = (H - (sp->trim ? sp->G / 2 : sp->G)) / kFusedSteps * kFusedSteps;
+        for (int k = 1; k <= 3; ++k) {
+            const int cut = (H - (H >> k)) / kFusedSteps * kFusedSteps;
+            if (cut > off.back() && cut + 64 < last_cut) off.push_back(cut);
+        }
+        if (last_cut > off.back()) off.push_back(last_cut);
+    }
+    off.push_back(H);
+    launch_rec(l, Ld, m->gi, outp, false, nullptr, 0, 0, 0, false, 1);
+    std::vector<int> dl(sp->S, 0), dr(sp->S, 0);      // what chunk k has finished so far: local columns [dl, dr) (empty: dl >= dr)
+    for (size_t p = 0; p + 1 < off.size(); ++p) {
+        launch_rec(l, Ld, m->gi, outp, false, nullptr, 0, off[p], off[p + 1] - off[p], true, 2);
+        m->last.rec_launches++;
+        if (!P.stream_out) continue;
+        hipEvent_t ev;
+        if ((rc = pool_event(m, &ev))) return rc;
+        HIP_TRY(hipEventRecord(ev, s));
+        for (int k = 0; k < sp->S; ++k) {
+            int lo = 0, hi = P.T;
+            for (int t = k * sp->B / kTileWin; t <= ((k + 1) * sp->B - 1) / kTileWin; ++t) {
+                const ScanRange r = split_tile_range(*sp, t, P.nb);
+                lo = std::max(lo, std::max(r.lo_r, r.mid - off[p + 1]));
+                hi = std::min(hi, std::min(r.hi_f, r.mid + off[p + 1]));
+            }
+            if (lo >= hi) continue;
+            if (dl[k] >= dr[k]) {
+                out_ranges.push_back({ev, lo, hi - lo, (int)p + 1, k});
+            } else {
+                if (lo < dl[k]) out_ranges.push_back({ev, lo, dl[k] - lo, (int)p + 1, k});
+                if (hi > dr[k]) out_ranges.push_back({ev, dr[k], hi - dr[k], (int)p + 1, k});
+            }
+            dl[k] = lo; dr[k] = hi;
+        }
+    }
     head_done = true;
     return MDK_OK;
 }
@@ -570,8 +628,8 @@ int Pass::layer_phased(int l, const LayerDev &Ld, float *outp, bool fuse, bool s
                 hipEvent_t hv;
                 if ((rc = pool_event(m, &hv))) return rc;
                 HIP_TRY(hipEventRecord(hv, m->side));
-                if (lo0 + len == hi0) out_ranges.push_back({hv, lo0, 2 * len, p});
-                else { out_ranges.push_back({hv, lo0, len, p}); out_ranges.push_back({hv, hi0, len, p}); }
+                if (lo0 + len == hi0) out_ranges.push_back({hv, lo0, 2 * len, p, 0});
+                else { out_ranges.push_back({hv, lo0, len, p, 0}); out_ranges.push_back({hv, hi0, len, p, 0}); }
             }
         }
     }
@@ -671,32 +729,36 @@ int Pass::copy_out() {
         // queue is still behind when the scan ends -- in half precision by 0.45 ms -- and a kernel behind the last recurrence
         // writes them home at the full PCIe rate while the queue finishes what it has (k_tail_to_host).
         TailRanges tail{};
+        const int first_launch = out_ranges.empty() ? 0 : out_ranges.front().launch;
         const int last_launch = out_ranges.empty() ? 0 : out_ranges.back().launch;
         int n_copy = 0;
+        hipEvent_t waited = nullptr;
         for (const OutRange &r : out_ranges) {
+            const int k = r.chunk;          // (a split call's ranges are per chunk: layer_final_head_ranged)
             // (half precision only: in fp32-parity mode the scan is slow enough for the queue to keep up, and the kernel would only
             // add its own 0.1 ms behind the last recurrence -- measured 7.95 -> 8.05 ms; half precision 5.74 -> 5.58 ms)
             // (two launches: one 5.68, two 5.57, three 5.76, four 6.2 ms per half-precision call -- what the kernel takes it takes
-            // AFTER the scan, what the queue takes it takes under it)
-            if (io->p_host_dev && P.hp && r.launch + 2 > last_launch && tail.n < 4 && out_ranges.size() > 4) {
-                tail.t0[tail.n] = r.t0; tail.nt[tail.n] = r.nt; tail.n++;
+            // AFTER the scan, what the queue takes it takes under it; a scan of fewer than three launches leaves by DMA alone)
+            if (io->p_host_dev && P.hp && r.launch + 2 > last_launch && last_launch - first_launch >= 2 && tail.n < kTailMax) {
+                tail.chunk[tail.n] = k; tail.t0[tail.n] = r.t0; tail.nt[tail.n] = r.nt; tail.n++;
                 continue;
             }
-            HIP_TRY(hipStreamWaitEvent(m->copy_out, r.ready, 0));
-            HIP_TRY(hipStreamWaitEvent(m->copy_out2, r.ready, 0));
-            for (int k = 0; k < sp->S; ++k) {
-                const int a = std::max(sp->core0[k], sp->start[k] + r.t0), b = std::min(sp->core0[k + 1], sp->start[k] + r.t0 + r.nt);
-                if (a >= b) continue;
-                // (copies alternate between two streams: each costs ~10 us of set-up on top of its bytes, and two DMA engines
-                // work side by side)
-                HIP_TRY(hipMemcpy2DAsync(io->p_host + (size_t)a * C, (size_t)sp->T * C * sizeof(float),
-                                         probs + (size_t)a * C, (size_t)sp->T * C * sizeof(float),
-                                         (size_t)(b - a) * C * sizeof(float), (size_t)sp->B, hipMemcpyDeviceToHost,
-                                         (n_copy++ & 1) ? m->copy_out2 : m->copy_out));
+            if (r.ready != waited) {        // (the ranges of one launch share its event: one wait per copy stream and launch)
+                HIP_TRY(hipStreamWaitEvent(m->copy_out, r.ready, 0));
+                HIP_TRY(hipStreamWaitEvent(m->copy_out2, r.ready, 0));
+                waited = r.ready;
             }
+            const int a = std::max(sp->core0[k], sp->start[k] + r.t0), b = std::min(sp->core0[k + 1], sp->start[k] + r.t0 + r.nt);
+            if (a >= b) continue;
+            // (copies alternate between two streams: each costs ~10 us of set-up on top of its bytes, and two DMA engines
+            // work side by side)
+            HIP_TRY(hipMemcpy2DAsync(io->p_host + (size_t)a * C, (size_t)sp->T * C * sizeof(float),
+                                     probs + (size_t)a * C, (size_t)sp->T * C * sizeof(float),
+                                     (size_t)(b - a) * C * sizeof(float), (size_t)sp->B, hipMemcpyDeviceToHost,
+                                     (n_copy++ & 1) ? m->copy_out2 : m->copy_out));
         }
         if (tail.n) {
-            hipLaunchKernelGGL(k_tail_to_host, dim3((unsigned)sp->B, (unsigned)(tail.n * sp->S)), dim3(256), 0, s, (const float *)probs,
+            hipLaunchKernelGGL(k_tail_to_host, dim3((unsigned)sp->B, (unsigned)tail.n), dim3(256), 0, s, (const float *)probs,
                                io->p_host_dev, *sp, tail, C);
             m->last.host_streamed |= 32;
         }

@@ -6,8 +6,9 @@
 // ---- split scan (scan_split.hpp): plan, run on the virtual batch, certify, fall back
 // The shape arithmetic of a split, free of any model state (also exported as mdk_split_plan for hosts and CPU tests).
 //   mode: 1 auto, n >= 2 forced chunk count; share: processes on this GPU; G: margin; budget: column budget of a pass
+static void plan_scan_ranges(SplitPlan &p, int trim);
 static bool plan_split_shape(int B, int T, int share, int mode, int G, size_t budget, SplitPlan &p) {
-    p.S = 1; p.B = B; p.T = T; p.Tv = T; p.G = 0;
+    p.S = 1; p.B = B; p.T = T; p.Tv = T; p.G = 0; p.trim = 0;
     if (B < 1 || T < 1 || mode < 1 || G < 8 || share < 1) return false;
     // The recurrence holds 8 windows per work-group and direction at most (fp32-parity mode): 1024 chunk-windows are
     // one round of work-groups on 256 CUs -- more than that queues (profiles/r3_experiments/scan_split/time_probe.txt).
@@ -28,7 +29,40 @@ static bool plan_split_shape(int B, int T, int share, int mode, int G, size_t bu
     p.S = S; p.G = G; p.Tv = Tv;
     for (int k = 0; k <= S; ++k) p.core0[k] = core0[k];
     for (int k = 0; k < S; ++k) p.start[k] = std::min(std::max(core0[k] - G, 0), T - Tv);
+    plan_scan_ranges(p, 0);
     return true;
+}
+
+// What the LAST layer scans of every chunk (option "scan_split_trim").  A chunk is run over its core plus G
+// columns on either side, but past its core, in scan order, the only reader of the last layer's state is the certificate's second
+// point, G/2 columns past the junction (scan_split.hpp k_split_verify): no head output comes from the G/2 columns behind it
+// (rec_fused.hpp FinRow clips to the core), no later layer exists and no certificate point lies there.  And before its core the
+// last layer is fed, for its first G/2 columns, by a previous layer that is itself still warming up.  In real columns:
+//   forward:  [k == 0 ? 0 : core0[k] - lead,   k == S-1 ? T : core0[k+1] + G/2)   upwards
+//   reverse:  [k == 0 ? 0 : core0[k] - G/2,    k == S-1 ? T : core0[k+1] + lead)  downwards
+//   trim 0: the whole virtual window;  1: lead = G, the trailing half-margin goes;  2: lead = G/2, the leading one as well
+// made local (- start[k]) and rounded outwards to the strip of the fused recurrence (8 columns; Tv is a multiple of 16), so that
+// the four launch lengths around any midpoint that is a multiple of 8 are whole strips (layout.hpp split_tile_range).
+// Level 1 vs level 0: interior chunks compute the same states from the same inputs.  An edge chunk's window is shifted inwards --
+// 2 G of lead, of which its scan now skips the first G, so its junction is warmed over G columns like every other -- and its
+// states differ until the two trajectories have merged.  Where the certificate holds they have, to the last bit, long before
+// the first delivered column: certified calls deliver level 0's bits on all seven weight sets (tests/test_split_trim_gpu.py,
+// profiles/l1_scan_range/README.md); that is measured, not guaranteed, and the junction difference of a REJECTED call differs
+// in its last digits.  Level 2 changes results at the rounding-noise level, and a model with a long memory needs the next larger
+// margin with it (`hp`: 256 instead of 192): the default is 1.
+static void plan_scan_ranges(SplitPlan &p, int trim) {
+    p.trim = p.S > 1 ? std::min(std::max(trim, 0), 2) : 0;
+    for (int k = 0; k < kMaxSplit; ++k) { p.lo_f[k] = p.lo_r[k] = 0; p.hi_f[k] = p.hi_r[k] = p.Tv; }
+    if (!p.trim) return;
+    const int half = p.G / 2, lead = p.trim >= 2 ? half : p.G;
+    auto down = [&](int t, int k) { return std::max(0, (t - p.start[k]) & ~7); };
+    auto up = [&](int t, int k) { return std::min(p.Tv, (t - p.start[k] + 7) & ~7); };
+    for (int k = 0; k < p.S; ++k) {
+        p.lo_f[k] = k == 0 ? 0 : down(p.core0[k] - lead, k);
+        p.lo_r[k] = k == 0 ? 0 : down(p.core0[k] - half, k);
+        p.hi_f[k] = k == p.S - 1 ? p.Tv : up(p.core0[k + 1] + half, k);
+        p.hi_r[k] = k == p.S - 1 ? p.Tv : up(p.core0[k + 1] + lead, k);
+    }
 }
 
 // The margin learner on a model that certifies iff the margin is >= `need` (0: never), with differences at the noise floor:
@@ -102,6 +136,40 @@ extern "C" int mdk_split_plan(int B, int T, int gpu_share, int scan_split, int m
     return MDK_OK;
 }
 
+extern "C" int mdk_split_scan_ranges(int B, int T, int gpu_share, int scan_split, int margin, int trim, mdk_split_ranges *out) {
+    if (!out) return fail(MDK_ERR_ARG, "null argument");
+    if (B < 0 || T < 0 || gpu_share < 1 || gpu_share > 8 || scan_split < 0 || scan_split > kMaxSplit || margin < 16 || margin > 4096 || margin % 8 ||
+        trim < 0 || trim > 2)
+        return fail(MDK_ERR_ARG, "bad argument (B=%d T=%d gpu_share=%d scan_split=%d margin=%d trim=%d)", B, T, gpu_share, scan_split, margin, trim);
+    SplitPlan p;
+    plan_split_shape(B, T, gpu_share, scan_split, margin, kMaxRowsPerPass, p);
+    plan_scan_ranges(p, trim);
+    memset(out, 0, sizeof(*out));
+    out->chunks = p.S; out->trim = p.trim;
+    for (int k = 0; k < p.S; ++k) {
+        out->lo_fwd[k] = p.lo_f[k]; out->hi_fwd[k] = p.hi_f[k]; out->lo_rev[k] = p.lo_r[k]; out->hi_rev[k] = p.hi_r[k];
+        out->mid[k] = split_mid(p.lo_f[k], p.hi_r[k]);
+    }
+    return MDK_OK;
+}
+
+extern "C" int mdk_split_tile_ranges(int B, int T, int gpu_share, int scan_split, int margin, int trim, int max_tiles, int *n_tiles, int *out) {
+    if (!n_tiles || (max_tiles > 0 && !out)) return fail(MDK_ERR_ARG, "null argument");
+    if (B < 1 || T < 1 || gpu_share < 1 || gpu_share > 8 || scan_split < 0 || scan_split > kMaxSplit || margin < 16 || margin > 4096 || margin % 8 ||
+        trim < 0 || trim > 2 || max_tiles < 0)
+        return fail(MDK_ERR_ARG, "bad argument (B=%d T=%d gpu_share=%d scan_split=%d margin=%d trim=%d)", B, T, gpu_share, scan_split, margin, trim);
+    SplitPlan p;
+    plan_split_shape(B, T, gpu_share, scan_split, margin, kMaxRowsPerPass, p);
+    plan_scan_ranges(p, trim);
+    const int nb = p.S * p.B;
+    *n_tiles = (nb + kTileWin - 1) / kTileWin;
+    for (int t = 0; t < *n_tiles && t < max_tiles; ++t) {
+        const ScanRange r = split_tile_range(p, t, nb);      // (what k_rec_fused and layer_final_head_ranged compute)
+        out[5 * t] = r.lo_f; out[5 * t + 1] = r.hi_f; out[5 * t + 2] = r.lo_r; out[5 * t + 3] = r.hi_r; out[5 * t + 4] = r.mid;
+    }
+    return MDK_OK;
+}
+
 static bool plan_split(const mdk_gru *m, int B, int T, SplitPlan &p) {
     static const int env_abl = getenv("MDK_ABLATE") ? atoi(getenv("MDK_ABLATE")) : 0;
     p.S = 1;
@@ -110,7 +178,10 @@ static bool plan_split(const mdk_gru *m, int B, int T, SplitPlan &p) {
     if (m->wide) return false;             // GRU(256): sequential scans only
     if (m->variant != MDK_VARIANT_MFMA || m->D != 2 || m->desc.num_layers != 2 || m->opt_ablate || env_abl) return false;
     if (m->layers[0].K > 16) return false;
-    return plan_split_shape(B, T, m->opt_gpu_share, P.opt_scan_split, P.margin_in_use(), m->max_rows_per_pass ? m->max_rows_per_pass : kMaxRowsPerPass, p);
+    if (!plan_split_shape(B, T, m->opt_gpu_share, P.opt_scan_split, P.margin_in_use(), m->max_rows_per_pass ? m->max_rows_per_pass : kMaxRowsPerPass, p))
+        return false;
+    plan_scan_ranges(p, m->opt_split_trim);
+    return true;
 }
 
 // A split call in two halves, so that the staged entry can enqueue the NEXT batch's forward before it waits for this one's
@@ -243,7 +314,7 @@ static int ensure_audit(mdk_gru *m, size_t n) {
 // certificate is still unread, or the sequential passes.  It is taken over if it is what this function would have enqueued now;
 // otherwise (an option, the learner or the back-off moved in between) it is waited for and forgotten.
 static bool same_split(const SplitPlan &a, const SplitPlan &b) {
-    if (a.S != b.S || a.B != b.B || a.T != b.T || a.Tv != b.Tv || a.G != b.G) return false;
+    if (a.S != b.S || a.B != b.B || a.T != b.T || a.Tv != b.Tv || a.G != b.G || a.trim != b.trim) return false;
     for (int k = 0; k < a.S; ++k) if (a.start[k] != b.start[k] || a.core0[k] != b.core0[k]) return false;
     return a.core0[a.S] == b.core0[b.S];
 }

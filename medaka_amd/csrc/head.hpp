@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void k_head_tiled(
     float *__restrict__ probs,        // [B][T][5]
     int B, int T, int n_tiles, int normalise,
     int t0, int nt,                   // columns [t0, t0 + nt) of every window
-    SplitPlan sp,
+    SplitPlanCore sp,
     const int *__restrict__ gate = nullptr)   // predicated pass (common.hpp gated_off)
 {
     constexpr int F = DIN * 128;
@@ -176,7 +176,7 @@ template <bool SPLIT>
 static __global__ __launch_bounds__(256) void k_head_combine(
     const float *__restrict__ lpart,  // [D][n_tiles][T][8][5]
     const float *__restrict__ lin_b,  // [5]
-    float *__restrict__ probs, int B, int T, int n_tiles, int D, int normalise, int t0, int nt, SplitPlan sp,
+    float *__restrict__ probs, int B, int T, int n_tiles, int D, int normalise, int t0, int nt, SplitPlanCore sp,
     const int *__restrict__ gate)     // predicated pass (common.hpp gated_off)
 {
     if (gated_off(gate)) return;
@@ -278,11 +278,12 @@ static __global__ __launch_bounds__(256) void k_decode(const float *__restrict__
 // tail on a 5.7 ms call (profiles/r6_experiments/README.md section 1).  At that moment the CUs have nothing to do -- a copy
 // kernel that talks to host memory BESIDE a recurrence stalls it (profiles/r4_experiments/README.md), behind the last one it
 // stalls nothing -- and a kernel writes pinned host memory at the full PCIe rate (54 GB/s, profiles/r2_host_path_probe.txt).
-// Block (w, j): window w, range r = j / S of chunk k = j % S: the real columns core_k /\ (start[k] + [t0[r], t0[r] + nt[r])).
-struct TailRanges { int n; int t0[4]; int nt[4]; };
-static __global__ __launch_bounds__(256) void k_tail_to_host(const float *__restrict__ probs, float *__restrict__ host, SplitPlan sp,
+// Block (w, r): window w, entry r: the real columns core_k /\ (start[k] + [t0[r], t0[r] + nt[r])) of chunk k = chunk[r].
+constexpr int kTailMax = 4 * kMaxSplit;      // the ranges of the last two launches: two per chunk and launch
+struct TailRanges { int n; int chunk[kTailMax]; int t0[kTailMax]; int nt[kTailMax]; };
+static __global__ __launch_bounds__(256) void k_tail_to_host(const float *__restrict__ probs, float *__restrict__ host, SplitPlanCore sp,
                                                              TailRanges tr, int C) {
-    const int w = blockIdx.x, r = blockIdx.y / sp.S, k = blockIdx.y % sp.S;
+    const int w = blockIdx.x, r = blockIdx.y, k = tr.chunk[r];
     const int a = max(sp.core0[k], sp.start[k] + tr.t0[r]), b = min(sp.core0[k + 1], sp.start[k] + tr.t0[r] + tr.nt[r]);
     if (a >= b) return;
     const size_t base = ((size_t)w * sp.T + a) * C;

@@ -38,7 +38,9 @@ __host__ __device__ inline int act_in_block(int dir, int w8, int q, int lane) {
 
 // Split scan (scan_split.hpp): a batch of B windows of T columns runs as S*B virtual windows of Tv columns.
 constexpr int kMaxSplit = 16;
-struct SplitPlan {
+// SplitPlanCore is what every kernel of a split call takes by value; only the last layer's fused recurrence (rec_fused.hpp) and
+// the host take the whole SplitPlan, with the scan ranges behind it.
+struct SplitPlanCore {
     int S = 1;                    // chunks per window (1 = not split)
     int B = 0, T = 0;             // the real batch
     int Tv = 0;                   // columns of a virtual window
@@ -46,5 +48,36 @@ struct SplitPlan {
     int start[kMaxSplit];         // first real column of chunk k
     int core0[kMaxSplit + 1];     // real columns [core0[k], core0[k+1]) are delivered from chunk k
 };
+struct SplitPlan : SplitPlanCore {
+    // Scan range of the LAST layer inside chunk k's virtual window (gru_split.hpp plan_scan_ranges; local columns, multiples of
+    // 8): the forward scan runs [lo_f, hi_f) upwards, the reverse scan [lo_r, hi_r) downwards, lo_f <= lo_r and hi_f <= hi_r.
+    // Always filled and always read: the final-head scan of EVERY split call takes its steps from these arrays (gru_pass.hpp
+    // layer_final_head_ranged, rec_fused.hpp `rng`); at trim = 0 they hold [0, Tv) for every chunk, which reproduces the layout a
+    // split scan had before there were ranges -- cut at Tv/2, the same launches, the outer margin as the last one.
+    int trim = 0;
+    int lo_f[kMaxSplit], hi_f[kMaxSplit];
+    int lo_r[kMaxSplit], hi_r[kMaxSplit];
+};
+
+// The last layer's scan range of one recurrence tile (8 consecutive virtual windows): the union over the chunks its windows
+// belong to -- a tile that mixes chunks (B not a multiple of 8) runs the wider range, extra warm-up and extra trailing columns
+// are harmless -- and the midpoint at which the scan is cut into its two halves.  The first half runs forward over [lo_f, mid)
+// and reverse over [mid, hi_r), the second forward over [mid, hi_f) and reverse over [lo_r, mid): what the second half finishes
+// lies inside what the other direction covered in the first.  Both direction work-groups of a tile, and the host, get the same.
+struct ScanRange { int lo_f, hi_f, lo_r, hi_r, mid; };
+__host__ __device__ inline int split_mid(int lo, int hi) { return (lo + hi) / 2 / 8 * 8; }
+__host__ __device__ inline ScanRange split_tile_range(const SplitPlan &p, int tile, int nb) {
+    const int w0 = tile * kTileWin, w1 = w0 + kTileWin - 1 < nb ? w0 + kTileWin - 1 : nb - 1;
+    const int k0 = w0 / p.B, k1 = w1 / p.B;
+    ScanRange r{p.lo_f[k0], p.hi_f[k0], p.lo_r[k0], p.hi_r[k0], 0};
+    for (int k = k0 + 1; k <= k1; ++k) {
+        r.lo_f = p.lo_f[k] < r.lo_f ? p.lo_f[k] : r.lo_f;
+        r.hi_f = p.hi_f[k] > r.hi_f ? p.hi_f[k] : r.hi_f;
+        r.lo_r = p.lo_r[k] < r.lo_r ? p.lo_r[k] : r.lo_r;
+        r.hi_r = p.hi_r[k] > r.hi_r ? p.hi_r[k] : r.hi_r;
+    }
+    r.mid = split_mid(r.lo_f, r.hi_r);
+    return r;
+}
 
 }  // namespace mdk

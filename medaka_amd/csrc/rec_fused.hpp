@@ -70,6 +70,8 @@ __global__ __launch_bounds__(512, 2) void k_rec_fused(
     const float *__restrict__ inv_scale_rec_p, const float *__restrict__ inv_scale_gi_p,
     const float *__restrict__ up_scale_rec_p, float a_scale,
     int reverse_mask, int s0, int ns,
+    int cold,                              // 1: the launch starts from h = 0 (also at s0 > 0); 0: it resumes from the stored h of step s0 - 1
+    int rng,                               // HEAD, split scan: the steps come from the plan, per work-group (below); 0: [s0, s0 + ns)
     const half8 *__restrict__ wlin_frag,   // HEAD: W_lin B-fragments [D][4 ksteps][2 hi/lo][64 lanes] (column n = class, n >= 5 zero)
     float lin_inv_scale,                   // HEAD: 1 / (kActScale * W_lin's operand scale)
     float *__restrict__ lpart,             // HEAD: partial logits [D][n_tiles][T][8 windows][5]
@@ -103,6 +105,22 @@ __global__ __launch_bounds__(512, 2) void k_rec_fused(
     const int c = lane & 15;
     const int g = lane >> 4;
     const bool reverse = (reverse_mask >> d) & 1;
+    // Split scan, last layer (`rng`; gru_split.hpp plan_scan_ranges): the work-group scans only the columns somebody reads of its
+    // 8 windows -- layout.hpp split_tile_range, wave-uniform.  rng = 1, the first half: forward [lo_f, mid), reverse
+    // [mid, hi_r), from h = 0.  rng = 2, a launch of the second half: the `ns` columns from `s0` columns past the midpoint in
+    // scan order, clipped to the range's end (a work-group whose range ends before the launch begins has nothing to do).
+    if constexpr (HEAD != 0) {
+        if (rng) {
+            const ScanRange r = split_tile_range(spl, tile, nb);
+            int a, b;                       // this launch's columns [a, b) of this direction
+            if (rng == 1) { a = reverse ? r.mid : r.lo_f; b = reverse ? r.hi_r : r.mid; }
+            else if (!reverse) { a = r.mid + s0; b = min(a + ns, r.hi_f); }
+            else { b = r.mid - s0; a = max(b - ns, r.lo_r); }
+            s0 = reverse ? T - b : a;
+            ns = b - a;
+            if (ns <= 0) return;
+        }
+    }
     const float inv_scale = inv_scale_rec_p[d];
     const float c_sig = -inv_scale * 1.44269504088896340736f;
     const float c_tanh = 2.0f * inv_scale * 1.44269504088896340736f;
@@ -226,7 +244,7 @@ __global__ __launch_bounds__(512, 2) void k_rec_fused(
             for (int sp = 0; sp < NS; ++sp) asm volatile("" ::"v"(wf[ks][gate][sp]));
     asm volatile("" ::"v"(bhn));
     __syncthreads();
-    if (s0 > 0) {   // resume: h of scan step s0 - 1 from the output, and its fp16 image (as k_rec_mfma)
+    if (!cold && s0 > 0) {   // resume: h of scan step s0 - 1 from the output, and its fp16 image (as k_rec_mfma)
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const float h = buf_load_float(orsrc, ovoff + q * 256, ocol(s0 - 1));

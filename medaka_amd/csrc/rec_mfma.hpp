@@ -497,7 +497,7 @@ static __global__ __launch_bounds__(256) void k_pack_x(
     half8 *__restrict__ xfrag,     // [n_wg][T][kXfragLanes]
     int B, int T, int I, int nq, int hp, int n_wg, float sx, int *__restrict__ oor,
     int t_lo, int nt,              // columns [t_lo, t_lo + nt) of every window (the host path streams x in time slabs)
-    SplitPlan sp,                  // sp.S > 1: B x T is the VIRTUAL batch of a split scan and x the real (sp.B, sp.T, I) one --
+    SplitPlanCore sp,              // sp.S > 1: B x T is the VIRTUAL batch of a split scan and x the real (sp.B, sp.T, I) one --
                                    // virtual window v = k * sp.B + w is columns [sp.start[k], +T) of window w (scan_split.hpp)
     const int *__restrict__ gate)  // predicated pass (common.hpp gated_off)
 {

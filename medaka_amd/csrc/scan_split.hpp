@@ -53,7 +53,7 @@ constexpr float kAuditTolHalf = 4.0e-4f;
 // operands straight from x (k_pack_x); the virtual batch is materialised only for the exact-projection fallback that an input
 // beyond fp16 range switches to on the device (k_pack_x raises the flag).
 static __global__ __launch_bounds__(256) void k_split_gather(const float *__restrict__ x, float *__restrict__ xv,
-                                                             SplitPlan p, int F, int vec, int t_lo, int nt, const int *__restrict__ cond,
+                                                             SplitPlanCore p, int F, int vec, int t_lo, int nt, const int *__restrict__ cond,
                                                              const int *__restrict__ gate) {
     if (gated_off(gate)) return;          // predicated pass (common.hpp)
     if (cond != nullptr && *cond == 0) return;
@@ -88,7 +88,7 @@ __device__ __forceinline__ float split_h(const float *__restrict__ act, int Tv, 
 //   a margin layer 1 is fed by a layer 0 that is itself still warming up in the other direction, by design).
 constexpr int kVerifyWin = 8;
 static __global__ __launch_bounds__(128) void k_split_verify(const float *__restrict__ act0, const float *__restrict__ act1,
-                                                             SplitPlan p, unsigned *__restrict__ flag) {
+                                                             SplitPlanCore p, unsigned *__restrict__ flag) {
     const int u = threadIdx.x;
     int z = blockIdx.y;
     const int point = z & 1; z >>= 1;

@@ -32,6 +32,29 @@ def split_plan(B, T, gpu_share=1, scan_split=1, margin=128):
             "last": list(t.last)[:n]}
 
 
+def split_scan_ranges(B, T, gpu_share=1, scan_split=1, margin=128, trim=1):
+    """What the last layer of a split call scans inside every chunk at "scan_split_trim" = `trim` (include/medaka_amd.h
+    `mdk_split_scan_ranges`; no device needed), in local columns of the chunk's virtual window:
+    {"chunks", "trim", "lo_fwd": [...], "hi_fwd": [...], "lo_rev": [...], "hi_rev": [...], "mid": [...]}."""
+    t = _lib.SplitRanges()
+    _lib.check(_lib.load().mdk_split_scan_ranges(int(B), int(T), int(gpu_share), int(scan_split), int(margin), int(trim),
+                                                 ctypes.byref(t)), "mdk_split_scan_ranges")
+    n = t.chunks
+    return {"chunks": n, "trim": t.trim, **{k: list(getattr(t, k))[:n] for k in ("lo_fwd", "hi_fwd", "lo_rev", "hi_rev", "mid")}}
+
+
+def split_tile_ranges(B, T, gpu_share=1, scan_split=1, margin=128, trim=1):
+    """What the device runs of a split call's last layer (include/medaka_amd.h `mdk_split_tile_ranges`; no device needed): one
+    (lo_fwd, hi_fwd, lo_rev, hi_rev, mid) per recurrence tile of 8 consecutive virtual windows -- the union over the chunks the
+    tile's windows belong to, and that union's midpoint."""
+    n = ctypes.c_int(0)
+    args = (int(B), int(T), int(gpu_share), int(scan_split), int(margin), int(trim))
+    _lib.check(_lib.load().mdk_split_tile_ranges(*args, 0, ctypes.byref(n), None), "mdk_split_tile_ranges")
+    buf = (ctypes.c_int * (5 * n.value))()
+    _lib.check(_lib.load().mdk_split_tile_ranges(*args, n.value, ctypes.byref(n), buf), "mdk_split_tile_ranges")
+    return [tuple(buf[5 * t:5 * t + 5]) for t in range(n.value)]
+
+
 def pass_plan(windows, T, num_features=10, num_layers=2, bidirectional=True, half=False, gpu_share=1, host_in=False,
               host_out=False, split_chunks=0, host_checks_range=False, lean=False, out_of_range_seen=False, gru_size=128):
     """How a pass of `windows` windows of T columns would be launched (include/medaka_amd.h `mdk_pass_plan`; no device needed):

@@ -53,6 +53,12 @@ class SplitShape(ctypes.Structure):
                 ("start", ctypes.c_int * 16), ("first", ctypes.c_int * 16), ("last", ctypes.c_int * 16)]
 
 
+class SplitRanges(ctypes.Structure):
+    _fields_ = [("chunks", ctypes.c_int), ("trim", ctypes.c_int),
+                ("lo_fwd", ctypes.c_int * 16), ("hi_fwd", ctypes.c_int * 16), ("lo_rev", ctypes.c_int * 16),
+                ("hi_rev", ctypes.c_int * 16), ("mid", ctypes.c_int * 16)]
+
+
 class PassShape(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in (
         "windows_per_group", "work_groups", "fuse_layer0", "fuse_projection", "fuse_head", "final_head",
@@ -81,6 +87,8 @@ ABI = {
     "mdk_gru_forward_pipelined": (_i, [_vp, ctypes.c_ulonglong, _i, _i, _vp, _vp]),
     "mdk_gru_drop_pending": (_i, [_vp]),
     "mdk_split_plan": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(SplitShape)]),
+    "mdk_split_scan_ranges": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(SplitRanges)]),
+    "mdk_split_tile_ranges": (_i, [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "mdk_margin_sim": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "mdk_pass_plan": (_i, [ctypes.POINTER(GruDesc), _i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(PassShape)]),
     "mdk_gru_device": (_i, [_vp]),

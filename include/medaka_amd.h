@@ -76,7 +76,9 @@ typedef struct {
     int fused_layers;     /* bit l set: layer l ran with its input projection fused into the recurrence (option
                              "fuse_proj"; its gi_ms is then 0 and its rec_ms covers both); bit 8: the classifier's Linear
                              ran inside the last layer's kernel as well ("fuse_head": head_ms is the combine kernel); bit 9: ... and the
-                             scan's second half wrote the probabilities itself ("final_head": no head kernel, head_ms ~ 0) */
+                             scan's second half wrote the probabilities itself ("final_head": no head kernel, head_ms ~ 0);
+                             bit 10 (ragged calls with timing enabled): the input left the fp16 range and layer 0 ran its unfused
+                             twin behind the exact projection */
 } mdk_gru_timing;
 
 /* What the last forward did about splitting the scan (option "scan_split" below). */
@@ -187,6 +189,20 @@ int mdk_gru_forward_dev(mdk_gru *m, const float *x_dev, int B, int T, float *pro
  * mdk_gru_forward_dev call at 200 x 10 000 (6.9 GB of gi for the 1000 x 2256 virtual batch, 6.1 GB for the repair's side-stream
  * projection), the same buffers a rejected synchronous call allocates. */
 int mdk_gru_forward_dev_async(mdk_gru *m, const float *x_dev, int B, int T, float *probs_dev, void *stream);
+
+/* Ragged forward: B windows of their own lengths in ONE call (no reference counterpart; the reference runs what it cannot
+ * batch one window at a time, prediction.py:191-209).  gru_size 128 only.
+ *   x: the windows one after another, sum(lengths) rows of num_features floats; probs: the same rows x num_classes.
+ *   lengths: B ints in HOST memory (both entries), each >= 1; consumed before the call returns.
+ * The probabilities of window i are, bit for bit, those of mdk_gru_forward for that window alone (B = 1) on the sequential scan,
+ * whatever shares the call.  The call is laid out for its longest window: ceil8(B) x max(lengths) columns have to fit the
+ * column budget of one pass ("max_rows_per_pass"), else MDK_ERR_ARG -- as for a null buffer, B < 0, a length < 1 or a
+ * gru_size 256 model.  B == 0 is a no-op.  Always a sequential scan: mdk_gru_get_split reports "not used".
+ * The device entry enqueues everything on `stream`, in order, and does not wait -- except: timing enabled; the first call at a
+ * shape that grows the workspace; and, with more than four ragged calls in flight, for the lengths of the call four before it to
+ * have reached the device (their page-locked staging is a ring of four). */
+int mdk_gru_forward_ragged(mdk_gru *m, const float *x_host, const int *lengths, int B, float *probs_host);
+int mdk_gru_forward_ragged_dev(mdk_gru *m, const float *x_dev, const int *lengths, int B, float *probs_dev, void *stream);
 
 /* Replaces `TorchModel.half()` (models.py:298-301): MDK_PREC_FP32 (default) / MDK_PREC_FP16. */
 int mdk_gru_set_precision(mdk_gru *m, int precision);
@@ -347,7 +363,8 @@ int mdk_margin_sim(int start, int adapt, int need, int n_calls, int *margins, in
  *   precision   MDK_PREC_*;  gpu_share  processes sharing the GPU;  host_io  bit 0: x comes from host memory, bit 1: the
  *   probabilities go to host memory;  split_chunks  > 1: the pass is the virtual batch of a split call;
  *   mode  bit 0: the caller looks at the fp16-range flag itself (split calls, host entries), bit 1: `lean` (an audit's scan),
- *         bit 2: the model has met out-of-range input before */
+ *         bit 2: the model has met out-of-range input before, bit 3: the pass of a ragged call (mdk_gru_forward_ragged; T is its
+ *         longest window) */
 typedef struct mdk_pass_shape {
     int windows_per_group;   /* 4, 8 or 16 */
     int work_groups;         /* per direction */

@@ -45,6 +45,7 @@ extern "C" const char *mdk_version(void) { return "medaka_amd 0.1 (gfx950)"; }
 #include "gru_wide_run.hpp"  // the GRU(256) forward: cluster recurrences, sequential scans
 #include "gru_split.hpp"     // split scan: plan, enqueue / finish, run_forward, start_call, enqueue_async / retire_one
 #include "gru_entries.hpp"   // mdk_gru_forward_dev / _stage_input / _forward_pipelined / _forward / counts, decoded
+#include "gru_ragged.hpp"    // mdk_gru_forward_ragged / _ragged_dev: windows of their own lengths in one call
 
 // ------------------------------------------------------------------------------------------
 // majority-vote model

@@ -27,7 +27,8 @@ static __global__ __launch_bounds__(128) void k_rec_exact(
     const float *__restrict__ gi,      // [D][M][384], folded bias
     const float *__restrict__ w_hh_t,  // [D][128][384]
     const float *__restrict__ b_hn,    // [D][128]
-    float *__restrict__ out, int B, int T, int out_stride, size_t gi_dir_stride, int reverse_mask)
+    float *__restrict__ out, int B, int T, int out_stride, size_t gi_dir_stride, int reverse_mask,
+    const int *__restrict__ lens = nullptr)   // ragged call: columns of every window, laid out T apart (null: T each)
 {
     __shared__ float hs[2][kH];
     const int j = threadIdx.x;
@@ -40,8 +41,11 @@ static __global__ __launch_bounds__(128) void k_rec_exact(
     hs[0][j] = 0.f;
     float hprev = 0.f;
     __syncthreads();
-    for (int step = 0; step < T; ++step) {
-        const int t = reverse ? T - 1 - step : step;
+    // A window scans its own columns only.  The padded rows [Tw, T) of `out` are NOT written (the MFMA path zeroes them):
+    // the layers above and the head are row-wise kernels, so what they compute from the stale rows stays in rows nobody delivers.
+    const int Tw = lens ? lens[seq] : T;
+    for (int step = 0; step < Tw; ++step) {
+        const int t = reverse ? Tw - 1 - step : step;
         const float *hc = hs[step & 1];
         float ar = 0.f, az = 0.f, an = 0.f;
         for (int k = 0; k < kH; ++k) {

@@ -152,6 +152,15 @@ struct mdk_gru : Ctx {
     unsigned long long *wexch = nullptr;     // [D][wide_exch_words(256)] granules + headers
     int *wstatus = nullptr;                  // [0] != 0: a cluster timed out
     int n_cus = 0;
+    // ragged calls (gru_ragged.hpp): lengths and offsets of the call on the device, behind a page-locked copy; the concatenated
+    // windows of a host call (padded x and probabilities live in x_dev / p_dev)
+    int *rag_meta = nullptr;
+    size_t rag_meta_cap = 0;
+    struct RagSlot { int *host = nullptr; size_t cap = 0; hipEvent_t read = nullptr; };   // page-locked words + the event behind their copy
+    RagSlot rag_slots[4];                    // a ring: a device call waits on the host only for the copy of the call four before it
+    unsigned rag_next = 0;
+    float *rag_x = nullptr, *rag_p = nullptr;
+    size_t rag_x_cap = 0, rag_p_cap = 0;
     int opt_wide_wait_ms = 3000;             // wall-clock budget of re-runs after a cluster time-out before MDK_ERR_DEVICE ("wide_wait_ms")
 };
 
@@ -240,6 +249,8 @@ extern "C" void mdk_gru_destroy(mdk_gru *m) {
     if (m->shares_copy_streams) { free_ctx(static_cast<Ctx &>(*m)); free_ctx(m->other); }
     else { free_ctx(m->other); free_ctx(static_cast<Ctx &>(*m)); }
     free_dev(m->aux_dev); free_dev(m->x_dev); free_dev(m->audit);
+    free_dev(m->rag_meta); free_dev(m->rag_x); free_dev(m->rag_p);
+    for (auto &rs : m->rag_slots) { if (rs.host) (void)hipHostFree(rs.host); if (rs.read) (void)hipEventDestroy(rs.read); }
     free_async(m);
     if (m->stage_stream) { (void)hipStreamSynchronize(m->stage_stream); (void)hipStreamDestroy(m->stage_stream); }
     for (auto &sl : m->stage) { free_dev(sl.dev); if (sl.ready) (void)hipEventDestroy(sl.ready); }

@@ -121,11 +121,17 @@ struct PassPlan {
     // the model (`oor_seen`) and repeats the call -- from then on with gi and the device-side decision.
     bool need_gi = true;
     bool wide = false;         // GRU(256): sequential cluster scans, nothing fused or overlapped (gru_wide_run.hpp)
+    // Ragged call (gru_ragged.hpp): T is the longest window and every window has its own length.  Only
+    // k_rec_mfma and k_rec_exact know lengths, and only k_head_tiled gives a ragged call the bits of its windows' single calls: the
+    // projection of layers >= 1, the head and the softmax stay unfused, gi exists, nothing streams (x and the result are
+    // concatenated in the caller's buffers: the entry pads and un-pads on the device).  The side-stream overlap stays.
+    bool ragged = false;
 };
 
 static int plan_pass(const mdk_gru *m, int nb, int T, const HostIO *io, const SplitPlan *sp, PassPlan &P, bool host_checks_range = false,
-                     bool lean = false) {
+                     bool lean = false, bool ragged = false) {
     P = PassPlan{};
+    P.ragged = ragged;
     P.nb = nb; P.T = T; P.D = m->D; P.L = m->desc.num_layers;
     P.exact = (m->variant == MDK_VARIANT_EXACT);
     P.n_tiles = (nb + kTileWin - 1) / kTileWin;
@@ -164,7 +170,8 @@ static int plan_pass(const mdk_gru *m, int nb, int T, const HostIO *io, const Sp
     while (nq < (P.hp ? 4 : 2) && ((n_win + 4 * nq - 1) / (4 * nq)) * D > cu_budget) nq *= 2;
     // half precision: 8-window work-groups while they fit the chip, so that layers >= 1 can run fused (rec_fused.hpp carries
     // 8 windows; 16-window groups fill only half the CUs at 1000 chunk-windows)
-    if (P.hp && nq == 4 && m->opt_fuse_proj && L >= 2 && ((n_win + 7) / 8) * D * m->opt_gpu_share <= 256) nq = 2;
+    // (a ragged pass never runs fused: it keeps the 16-window groups, one round of work-groups within the budget)
+    if (P.hp && nq == 4 && !ragged && m->opt_fuse_proj && L >= 2 && ((n_win + 7) / 8) * D * m->opt_gpu_share <= 256) nq = 2;
     // `lean` (the audit's sequential scan): whatever the batch, the regime that needs no gi in HBM -- 8-window work-groups with
     // the projection inside the recurrence -- so that an audit allocates nothing (and, above all, FREES nothing: see run_forward)
     if (lean && nq < 2 && m->opt_fuse_proj && L >= 2) nq = 2;
@@ -212,6 +219,11 @@ static int plan_pass(const mdk_gru *m, int nb, int T, const HostIO *io, const Sp
     // KERNEL beside a recurrence that holds every CU crawls: a split call without the final head leaves as one copy)
     P.stream_out = ((P.io_out && P.can_chunk) || (P.sp_out && P.can_chunk_sp && P.final_head)) && L >= 2 && m->opt_stream_host;
     P.need_gi = !P.fuse0 || (L >= 2 && !P.fuse_proj) || !host_checks_range || m->oor_seen;
+    if (ragged) {
+        P.fuse_proj = P.fuse_head = P.final_head = P.stream_in = P.stream_out = false;
+        P.overlap = overlap_ok;
+        P.need_gi = true;
+    }
     return MDK_OK;
 }
 
@@ -229,6 +241,7 @@ struct Pass {
                                              // after its certificate kernel) instead of a wait on `s`
     const int *gate;                         // predicated pass (the stream-ordered entry's repair and audit): every kernel of the
                                              // pass returns at once while *gate != 0 (common.hpp gated_off); null = always runs
+    const int *lens = nullptr;               // ragged pass (PassPlan::ragged): device, columns of every window slot of the recurrence grid
     struct OutRange { hipEvent_t ready; int t0, nt; int launch; int chunk; };   // chunk: split calls only (local columns of that chunk)
     std::vector<OutRange> out_ranges;        // column ranges to copy out; issued after every launch is enqueued, because a
                                              // copy into pageable memory may block the calling thread until it is done
@@ -340,14 +353,17 @@ void Pass::launch_gi_small(int l, const LayerDev &Ld, const int *cond) {
                        Ld.w_ih_t, Ld.bias_gi, m->gi, P.nb, T, Ld.K, P.n_tiles, tpb, Ld.up_scale_rec, cond, 1, gate);
 }
 
-#define MDK_LAUNCH_REC_T(NQV, XIN, HPF, A, DSV, CND, WANT)                                         \
-    hipLaunchKernelGGL((k_rec_mfma<MDK_PF, NQV, XIN, HPF, 0, A, DSV>), rgrid(), dim3(512), 0, s, gi_src, m->xfrag, \
+#define MDK_LAUNCH_REC_T(NQV, XIN, HPF, A, DSV, RAGV, CND, WANT)                                   \
+    hipLaunchKernelGGL((k_rec_mfma<MDK_PF, NQV, XIN, HPF, 0, A, DSV, RAGV>), rgrid(), dim3(512), 0, s, gi_src, m->xfrag, \
                        Ld.wx_frag, Ld.whh_frag, Ld.b_hn, outp, P.n_tiles, P.T, P.D, Ld.inv_scale_rec,    \
-                       reverse_mask(), CND, WANT, rs0, rns, gate)
-// deferred HBM store of h_t (default) or the store behind the gate math; ablation builds use the latter
+                       reverse_mask(), CND, WANT, rs0, rns, gate, RAGV ? lens : (const int *)nullptr)
+// deferred HBM store of h_t (default) or the store behind the gate math; ablation builds use the latter; a ragged pass runs the
+// twins that know lengths
 #define MDK_LAUNCH_REC(NQV, XIN, HPF, A, CND, WANT)                                                \
-    do { if ((A) == 0 && m->opt_deferred_store) MDK_LAUNCH_REC_T(NQV, XIN, HPF, 0, true, CND, WANT); \
-         else MDK_LAUNCH_REC_T(NQV, XIN, HPF, A, false, CND, WANT); } while (0)
+    do { if ((A) == 0 && P.ragged && m->opt_deferred_store) MDK_LAUNCH_REC_T(NQV, XIN, HPF, 0, true, true, CND, WANT); \
+         else if ((A) == 0 && P.ragged) MDK_LAUNCH_REC_T(NQV, XIN, HPF, 0, false, true, CND, WANT); \
+         else if ((A) == 0 && m->opt_deferred_store) MDK_LAUNCH_REC_T(NQV, XIN, HPF, 0, true, false, CND, WANT); \
+         else MDK_LAUNCH_REC_T(NQV, XIN, HPF, A, false, false, CND, WANT); } while (0)
 
 // one recurrence launch over the scan steps [rs0, rs0 + rns) of layer l.
 // `fin`: this launch's columns are complete (second half of a bidirectional scan, any step of a one-directional
@@ -388,14 +404,16 @@ void Pass::launch_rec(int l, const LayerDev &Ld, const float *gi_src, float *out
 // the unfused twin of a fused layer 0: runs only if the range flag is up.  It is instantiated with a different ring depth
 // only so that profilers show it under its own symbol (its launches are empty unless the range flag is raised)
 void Pass::launch_rec_fallback(const LayerDev &Ld, const float *gi_src, float *outp, const int *cnd, int rs0, int rns) {
-#define MDK_LAUNCH_FB(NQV, HPF)                                                                    \
-    hipLaunchKernelGGL((k_rec_mfma<MDK_PF - 1, NQV, false, HPF>), rgrid(), dim3(512), 0, s, gi_src, m->xfrag, \
+#define MDK_LAUNCH_FB_T(NQV, HPF, RAGV)                                                            \
+    hipLaunchKernelGGL((k_rec_mfma<MDK_PF - 1, NQV, false, HPF, 0, 0, false, RAGV>), rgrid(), dim3(512), 0, s, gi_src, m->xfrag, \
                        Ld.wx_frag, Ld.whh_frag, Ld.b_hn, outp, P.n_tiles, P.T, P.D, Ld.inv_scale_rec,    \
-                       reverse_mask(), cnd, 1, rs0, rns, gate)
+                       reverse_mask(), cnd, 1, rs0, rns, gate, RAGV ? lens : (const int *)nullptr)
+#define MDK_LAUNCH_FB(NQV, HPF) do { if (P.ragged) MDK_LAUNCH_FB_T(NQV, HPF, true); else MDK_LAUNCH_FB_T(NQV, HPF, false); } while (0)
     const int nq = P.nq;
     if (P.hp) { if (nq == 1) MDK_LAUNCH_FB(1, true); else if (nq == 2) MDK_LAUNCH_FB(2, true); else MDK_LAUNCH_FB(4, true); }
     else { if (nq == 1) MDK_LAUNCH_FB(1, false); else MDK_LAUNCH_FB(2, false); }
 #undef MDK_LAUNCH_FB
+#undef MDK_LAUNCH_FB_T
 }
 
 #ifdef MDK_DEBUG_HOOKS
@@ -440,7 +458,7 @@ int Pass::run_exact() {
         if ((rc = tm.end())) return rc;
         if ((rc = tm.begin(SLOT_REC0 + l))) return rc;
         hipLaunchKernelGGL(k_rec_exact, dim3(nb, D), dim3(128), 0, s, m->gi, Ld.w_hh_t, Ld.b_hn, outp,
-                           nb, T, out_stride, gi_dir_stride, reverse_mask());
+                           nb, T, out_stride, gi_dir_stride, reverse_mask(), P.ragged ? lens : (const int *)nullptr);
         if ((rc = tm.end())) return rc;
         m->last.rec_launches++;
         in = outp;
@@ -824,8 +842,9 @@ int Pass::run() {
 
 static int forward_pass(mdk_gru *m, const PassPlan &P, const float *x, float *probs, hipStream_t s,
                         EvTimer &tm, const HostIO *io, const SplitPlan *sp = nullptr, std::vector<hipEvent_t> *join_later = nullptr,
-                        const int *gate = nullptr) {
+                        const int *gate = nullptr, const int *lens = nullptr) {
     Pass pass{m, P, x, probs, s, tm, io, sp, join_later, gate};
+    pass.lens = lens;
     return pass.run();
 }
 

@@ -113,7 +113,8 @@ extern "C" int mdk_pass_plan(const mdk_gru_desc *desc, int precision, int gpu_sh
     SplitPlan sp;
     sp.S = split_chunks;
     PassPlan P;
-    const int rc = plan_pass(&m, windows, T, (host_io & 3) ? &io : nullptr, split_chunks > 1 ? &sp : nullptr, P, (mode & 1) != 0, (mode & 2) != 0);
+    const int rc = plan_pass(&m, windows, T, (host_io & 3) ? &io : nullptr, split_chunks > 1 ? &sp : nullptr, P, (mode & 1) != 0, (mode & 2) != 0,
+                             (mode & 8) != 0);
     if (rc) return rc;
     memset(out, 0, sizeof(*out));
     out->windows_per_group = 4 * P.nq; out->work_groups = P.n_wg;

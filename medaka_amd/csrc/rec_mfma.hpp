@@ -67,7 +67,12 @@ constexpr int kHBufBytes = 4 * kHKStride;     // 4096 B per buffer
 // DS (GRU, barrier schedule): the HBM store of h_t is deferred to the MFMA phase of step t+1 (h_prev still
 // holds the value), so its address arithmetic and issue leave the tail between the last MFMA and the LDS
 // publish.  Ablations (profiles/r2_ablation.txt): the stores cost ~115 cycles of a ~1380-cycle step.
-template <int PF, int NQ, bool XIN, bool HP, int CELL = 0, int ABL = 0, bool DS = false>
+// RAG (GRU, ragged call: DESIGN.md section 4.9c): every window has its own length, lens[window slot of the grid] (0 behind the
+// batch); the call is laid out for the longest, T.  The state of a window is forced to zero at every scan step whose column
+// lies outside [0, len) -- by a select on the step's new h, BEFORE it is kept for the next blend, published or stored -- so a reverse scan arrives at the window's
+// last real column with h = 0 and a zero image, exactly as a scan of that window alone starts, and the padding of the
+// activations is zero for the layer above.  The deferred store and the resume path see the zero because they see hprev.
+template <int PF, int NQ, bool XIN, bool HP, int CELL = 0, int ABL = 0, bool DS = false, bool RAG = false>
 __global__ __launch_bounds__(512, 2) void k_rec_mfma(
     const float *__restrict__ gi,      // !XIN: gi_t (layout.hpp), folded bias, PRE-SCALED by S_d
     const half8 *__restrict__ xfrag,   //  XIN: packed x A-fragments [work-group][t][kXfragLanes]
@@ -79,7 +84,8 @@ __global__ __launch_bounds__(512, 2) void k_rec_mfma(
     const int *__restrict__ cond, int want,
     int s0, int ns,   // steps [s0, s0 + ns) of the scan (scan step s is t = s, or T-1-s when reversed);
                       // s0 > 0 resumes from the h this kernel stored at scan step s0 - 1 (GRU only)
-    const int *__restrict__ gate = nullptr)   // predicated pass (common.hpp gated_off)
+    const int *__restrict__ gate = nullptr,   // predicated pass (common.hpp gated_off)
+    const int *__restrict__ lens = nullptr)   // RAG: columns of every window slot of the grid [gridDim.x * 4 * NQ]
 {
     __shared__ __attribute__((aligned(16))) unsigned char hbuf[2 * kHBufBytes];
     if (gated_off(gate)) return;
@@ -109,6 +115,7 @@ __global__ __launch_bounds__(512, 2) void k_rec_mfma(
     static_assert(!(XIN && CELL), "the fused input projection exists for the GRU layer 0 only");
     static_assert(!(CELL && ABL), "ablation builds exist for the GRU cell only");
     static_assert(HP || NQ <= 2, "fp32-parity mode carries at most 2 windows per lane");
+    static_assert(!(RAG && (CELL || ABL)), "ragged calls: GRU production builds only");
     half8 wf[4][NG][NS];
     {
         const half8 *wp = wfrag + ((size_t)(d * 8 + w8) * (8 * NG)) * 64 + lane;
@@ -141,10 +148,13 @@ __global__ __launch_bounds__(512, 2) void k_rec_mfma(
     const float *gp[NQ];
     float *op[NQ];
     bool live[NQ];
+    int edge[NQ];      // RAG: scan steps [0, edge) lie inside the window (forward), or steps [edge, T) do (reverse)
+    auto inside = [&](int q, int step) { return (step < edge[q]) != reverse; };
     auto stores = [&](int q) { if constexpr (NQ == 4) return live[q]; else return true; };
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
         int win = blockIdx.x * (4 * NQ) + NQ * g + q;
+        if constexpr (RAG) { const int len = lens[win]; edge[q] = reverse ? T - len : len; }
         // only NQ = 4 can run past the padding (a tile count that is odd): those lanes load from the last window, for
         // the addresses' sake, and store nothing -- with the fused layer-0 input their x rows are zero, not a copy
         live[q] = win < n_tiles * kTileWin;
@@ -386,7 +396,8 @@ __global__ __launch_bounds__(512, 2) void k_rec_mfma(
                         const float an = __builtin_fmaf(rr[q], tn, gnv[q]);
                         const float e = __builtin_amdgcn_exp2f(an * c_tanh);
                         const float n = __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + e), 1.0f);
-                        const float h = __builtin_fmaf(zz[q], hprev[q] - n, n);
+                        float h = __builtin_fmaf(zz[q], hprev[q] - n, n);
+                        if constexpr (RAG) h = inside(q, step) ? h : 0.f;
                         hprev[q] = h;
                         hn[q] = h;
                         if constexpr (!(ABL & 16) && !DS) { if (step < s_end && stores(q)) op[q][0] = h; }

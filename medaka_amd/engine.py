@@ -56,17 +56,47 @@ def split_tile_ranges(B, T, gpu_share=1, scan_split=1, margin=128, trim=1):
 
 
 def pass_plan(windows, T, num_features=10, num_layers=2, bidirectional=True, half=False, gpu_share=1, host_in=False,
-              host_out=False, split_chunks=0, host_checks_range=False, lean=False, out_of_range_seen=False, gru_size=128):
+              host_out=False, split_chunks=0, host_checks_range=False, lean=False, out_of_range_seen=False, gru_size=128,
+              ragged=False):
     """How a pass of `windows` windows of T columns would be launched (include/medaka_amd.h `mdk_pass_plan`; no device needed):
     work-group granularity, what is fused / streamed, and whether the gi workspace is needed.  `gru_size` = 256: the
-    sequential cluster scan (work_groups = CUs it holds), nothing fused or streamed."""
+    sequential cluster scan (work_groups = CUs it holds), nothing fused or streamed.  `ragged`: the pass of a ragged call
+    (`GruEngine.forward_ragged_host`) whose longest window has T columns."""
     desc = _lib.GruDesc(int(num_features), int(gru_size), int(num_layers), int(bool(bidirectional)), 5, 1)
     t = _lib.PassShape()
-    mode = (1 if host_checks_range else 0) | (2 if lean else 0) | (4 if out_of_range_seen else 0)
+    mode = (1 if host_checks_range else 0) | (2 if lean else 0) | (4 if out_of_range_seen else 0) | (8 if ragged else 0)
     _lib.check(_lib.load().mdk_pass_plan(ctypes.byref(desc), 1 if half else 0, int(gpu_share), int(windows), int(T),
                                          (1 if host_in else 0) | (2 if host_out else 0), int(split_chunks), mode, ctypes.byref(t)),
                "mdk_pass_plan")
     return {n: (getattr(t, n) if n in ("windows_per_group", "work_groups") else bool(getattr(t, n))) for n, _ in t._fields_}
+
+
+def ragged_window_cap(half=False, bidirectional=True, gpu_share=1):
+    """Windows of one ragged call that still run as ONE round of recurrence work-groups: the largest count for which the ragged
+    `pass_plan` keeps work_groups x directions within the CU budget plan_pass itself uses (232 // gpu_share) at the largest tile
+    (8 windows per work-group in fp32-parity mode, 16 in half precision)."""
+    groups = (232 // max(1, int(gpu_share))) // (2 if bidirectional else 1)
+    return max(1, groups) * (16 if half else 8)
+
+
+def ragged_calls(lengths, half=False, bidirectional=True, gpu_share=1, max_cols=1 << 21):
+    """Group windows of different lengths into ragged calls: lists of indices into `lengths`, one list per call.  Pure
+    function, no device.  Longest first (stable), then greedily while a call stays within one round of work-groups
+    (`ragged_window_cap`) and its padded area ceil8(windows) x longest window stays within `max_cols` columns -- 2 Mi columns is
+    the area of the production batch (200 x 10 000), which the sequential workspace is sized for anyway.  A window that alone
+    exceeds `max_cols` is a call by itself."""
+    lengths = [int(n) for n in lengths]
+    cap = ragged_window_cap(half, bidirectional, gpu_share)
+    order = sorted(range(len(lengths)), key=lambda i: -lengths[i])          # (sorted() is stable)
+    calls, cur = [], []
+    for i in order:
+        if cur and (len(cur) + 1 > cap or (len(cur) + 1 + 7) // 8 * 8 * lengths[cur[0]] > max_cols):
+            calls.append(cur)
+            cur = []
+        cur.append(i)
+    if cur:
+        calls.append(cur)
+    return calls
 
 
 class DeviceBuffer:
@@ -207,6 +237,36 @@ class GruEngine:
         _lib.check(_lib.load().mdk_gru_forward(self._h, x.ctypes.data, B, T, out.ctypes.data),
                    "mdk_gru_forward")
         return out
+
+    def forward_ragged_host(self, xs):
+        """Windows of their own lengths in one call (include/medaka_amd.h `mdk_gru_forward_ragged`): a list of (T_i, F)
+        float32 host arrays -> a list of (T_i, C) float32 host arrays, each bit for bit what `forward_host(x_i[None])[0]`
+        returns on the sequential scan (synchronous).  The results are views of one array."""
+        xs = [np.asarray(x, dtype=np.float32) for x in xs]
+        for x in xs:
+            if x.ndim != 2 or x.shape[1] != self.num_features:
+                raise ValueError(f"expected (T, {self.num_features}) windows, got {x.shape}")
+        if not xs:
+            return []
+        lengths = np.array([x.shape[0] for x in xs], dtype=np.intc)
+        cat = np.ascontiguousarray(np.concatenate(xs, axis=0)) if len(xs) > 1 else np.ascontiguousarray(xs[0])
+        out = np.empty((cat.shape[0], self.num_classes), dtype=np.float32)
+        self.forward_ragged_ptr(cat.ctypes.data, lengths, out.ctypes.data, host=True)
+        ends = np.cumsum(lengths)
+        return [out[e - n:e] for e, n in zip(ends, lengths)]
+
+    def forward_ragged_ptr(self, x_ptr, lengths, out_ptr, stream=None, host=False):
+        """Raw-pointer ragged forward: x and out hold the windows one after another (sum(lengths) rows) -- host pointers
+        (`host=True`) or device pointers + hipStream_t (`mdk_gru_forward_ragged_dev`: enqueued on the stream, not waited
+        for).  `lengths` is a host sequence of ints either way."""
+        lengths = np.ascontiguousarray(lengths, dtype=np.intc)
+        lp = lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        L = _lib.load()
+        if host:
+            _lib.check(L.mdk_gru_forward_ragged(self._h, x_ptr, lp, len(lengths), out_ptr), "mdk_gru_forward_ragged")
+        else:
+            _lib.check(L.mdk_gru_forward_ragged_dev(self._h, x_ptr, lp, len(lengths), out_ptr, stream),
+                       "mdk_gru_forward_ragged_dev")
 
     def forward_counts_host(self, counts, depth, probs=True, decoded=False, out=None):
         """Raw pileup counts (B,T,F) uint16 + per-column depth (B,T) uint32 -> probabilities and/or

@@ -13,6 +13,10 @@ the reference implementation -- the engine itself never runs on the CPU.  `Laten
 models with cnn_size = 128 and lstm_size = 128, or lstm_size = 384 uni-directional (the bundled
 `rl_lstm384`), are accelerated too.
 
+`install()` also wraps `medaka.prediction.run_prediction`: the remainder pass of `medaka inference` (prediction.py:191-209, one
+window per call) runs its windows side by side in ragged calls (`GRUModel.predict_on_ragged`); `MEDAKA_AMD_RAGGED=0` keeps the
+reference's loop.
+
 Opt in with `MEDAKA_AMD=1` in the environment of `medaka inference` or by
 calling `install()` before `medaka.prediction.predict(args)`.  `MEDAKA_AMD=strict` additionally turns every
 "keeping the reference model" decision on a HIP device into an `EngineRequired` error -- the launcher
@@ -144,10 +148,87 @@ def _fast_collate(orig):
     return collate
 
 
-def install(collate=None):
-    """Patch `medaka.datastore.ModelStoreTGZ.load_model` (the model swap) and -- unless `collate` is False or
+def _env_on(name):
+    return os.environ.get(name, "1").strip().lower() not in ("0", "off", "false")
+
+
+def predict_remainders(batches, model, write, flush_at=None):
+    """The body of the reference's remainder pass (prediction.py:191-209 -> run_prediction with batch_size 1, unchunked:
+    "everything is a different size, cant batch") on ragged calls, free of reference types.
+
+    `batches` yields (data, batch) pairs as the reference's DataLoader does at batch_size 1: `data` the samples, `batch.features`
+    their (1, T, F) tensor.  Samples are collected until `flush_at` = (windows, columns) are pending -- default: the window cap
+    of one ragged call for this model (`engine.ragged_window_cap`) and the 2 Mi columns `predict_on_ragged` packs into one call
+    -- or the loader ends; `model.predict_on_ragged` then runs them side by side and every (sample, probabilities, features)
+    goes to `write`, in the loader's order.  Returns the number of `predict_on_ragged` calls."""
+    from medaka_amd import engine as _engine
+    from medaka_amd import models as _models
+    if flush_at is None:
+        flush_at = (_engine.ragged_window_cap(bool(getattr(model, "half_precision", False)), bool(getattr(model, "bidirectional", True)),
+                                              _models.gpu_share()), 1 << 21)
+    max_windows, max_cols = flush_at
+    pending, cols, calls = [], 0, 0
+
+    def flush():
+        nonlocal pending, cols, calls
+        if pending:
+            probs = model.predict_on_ragged([feat for _, feat in pending])
+            calls += 1
+            for (sample, feat), p in zip(pending, probs):
+                write(sample, p, feat)
+        pending, cols = [], 0
+
+    for data, batch in batches:
+        for sample, feat in zip(data, batch.features):
+            pending.append((sample, feat))
+            cols += int(feat.shape[0])
+        if len(pending) >= max_windows or cols >= max_cols:
+            flush()
+    flush()
+    return calls
+
+
+def _ragged_run_prediction(orig):
+    """`medaka.prediction.run_prediction` with its remainder form -- batch_size 1, no chunking: prediction.py:204-209 -- routed
+    through `predict_remainders` when the model can run ragged calls; every other call is the reference's own function.  The
+    loader, the data store and the way a sample is amended and written are the reference's (prediction.py:23-37, :47-52),
+    resolved at call time."""
+    @functools.wraps(orig)
+    def run_prediction(output, bam, regions, model, feature_encoder, chunk_len, chunk_ovlp, batch_size=200,
+                       save_features=False, enable_chunking=True, bam_workers=2):
+        if not (batch_size == 1 and not enable_chunking and hasattr(model, "predict_on_ragged")):
+            return orig(output, bam, regions, model, feature_encoder, chunk_len, chunk_ovlp, batch_size=batch_size,
+                        save_features=save_features, enable_chunking=enable_chunking, bam_workers=bam_workers)
+        import medaka.datastore
+        import medaka.prediction
+        from medaka_amd import torch_ext as _te
+        # no early hand-over of these one-window batches -- nobody redeems their tokens: switched off BEFORE the loader's Batcher
+        # thread exists, and on again afterwards only if the engine is still open and nobody registered another meanwhile
+        target = _te.stage_target()
+        if target is not None:
+            _te.forget_stage_target(target)
+        try:
+            loader = medaka.prediction.DataLoader(
+                bam, regions, batch_size, batch_cache_size=8, bam_workers=bam_workers, feature_encoder=feature_encoder,
+                chunk_len=chunk_len, chunk_overlap=chunk_ovlp, enable_chunking=enable_chunking)
+            with medaka.datastore.DataStore(output, 'a') as ds:
+                def write(sample, probs, feat):
+                    ds.write_sample(sample.amend(label_probs=probs, features=feat if save_features else None))
+                calls = predict_remainders(loader, model, write)
+        finally:
+            if target is not None and target._h and _te.stage_target() is None:
+                _te.set_stage_target(target)
+        remainders = loader.remainders
+        logger.info("medaka_amd: %d ragged call(s) for the remainder pass, %d remainder regions", calls, len(remainders))
+        return remainders
+    return run_prediction
+
+
+def install(collate=None, ragged=None):
+    """Patch `medaka.datastore.ModelStoreTGZ.load_model` (the model swap), -- unless `collate` is False or
     `MEDAKA_AMD_COLLATE=0` -- `medaka.torch_ext.Batch.collate` (batch assembly in the Batcher thread,
-    prediction.py:356-370).  Idempotent."""
+    prediction.py:356-370) and -- unless `ragged` is False or `MEDAKA_AMD_RAGGED=0` -- `medaka.prediction.run_prediction`
+    (the remainder pass on ragged calls; `predict()` resolves it as a module global).  Idempotent."""
     import medaka.datastore as ds
 
     if "load_model" not in _ORIG:
@@ -162,11 +243,17 @@ def install(collate=None):
         _ORIG["load_model"] = orig
         ds.ModelStoreTGZ.load_model = load_model
     if collate is None:
-        collate = os.environ.get("MEDAKA_AMD_COLLATE", "1").strip().lower() not in ("0", "off", "false")
+        collate = _env_on("MEDAKA_AMD_COLLATE")
     if collate and "collate" not in _ORIG:
         import medaka.torch_ext as rte
         _ORIG["collate"] = rte.Batch.__dict__["collate"]           # the classmethod object itself
         rte.Batch.collate = classmethod(_fast_collate(_ORIG["collate"].__func__))
+    if ragged is None:
+        ragged = _env_on("MEDAKA_AMD_RAGGED")
+    if ragged and "run_prediction" not in _ORIG:
+        import medaka.prediction as mp
+        _ORIG["run_prediction"] = mp.run_prediction
+        mp.run_prediction = _ragged_run_prediction(_ORIG["run_prediction"])
 
 
 def uninstall():
@@ -176,6 +263,9 @@ def uninstall():
     if "collate" in _ORIG:
         import medaka.torch_ext as rte
         rte.Batch.collate = _ORIG.pop("collate")
+    if "run_prediction" in _ORIG:
+        import medaka.prediction as mp
+        mp.run_prediction = _ORIG.pop("run_prediction")
 
 
 def install_from_env():

@@ -75,6 +75,8 @@ ABI = {
     "mdk_gru_forward": (_i, [_vp, _vp, _i, _i, _vp]),
     "mdk_gru_forward_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "mdk_gru_forward_dev_async": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "mdk_gru_forward_ragged": (_i, [_vp, _vp, ctypes.POINTER(_i), _i, _vp]),
+    "mdk_gru_forward_ragged_dev": (_i, [_vp, _vp, ctypes.POINTER(_i), _i, _vp, _vp]),
     "mdk_gru_set_precision": (_i, [_vp, _i]),
     "mdk_gru_set_variant": (_i, [_vp, _i]),
     "mdk_gru_set_normalise": (_i, [_vp, _i]),

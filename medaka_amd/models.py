@@ -135,6 +135,9 @@ def _hip_device_index(dev):
     return dev.index if dev.index is not None else torch.cuda.current_device()
 
 
+_RAGGED_PASS_COLUMNS = 16 << 20      # the engine's default column budget of one pass (csrc/gru_pass.hpp kMaxRowsPerPass)
+
+
 class GRUModel(CountsMatrixModel):
     """Bidirectional GRU on counts matrix -- HIP engine behind the reference interface."""
 
@@ -239,6 +242,39 @@ class GRUModel(CountsMatrixModel):
             eng.forward_ptr(x.data_ptr(), B, T, out.data_ptr(), host=True)
             return out
         return self.forward(x).detach().cpu()
+
+    def predict_on_ragged(self, windows, max_cols=1 << 21):
+        """Windows of different lengths side by side (no reference counterpart: prediction.py:191-209 runs them one at a time,
+        "everything is a different size, cant batch").  `windows`: host tensors or arrays (T_i, num_features); returns float32
+        host tensors (T_i, 5) IN INPUT ORDER, each bit for bit what a single-window `predict_on_batch` returns on the
+        sequential scan.  The windows are grouped by `engine.ragged_calls` (longest first, one round of work-groups and at most
+        `max_cols` padded columns per call) and every group is one `forward_ragged_host`.  `half()`, `normalise` and
+        `exact_kernels` are honoured as in `predict_on_batch`.  A gru_size 256 model runs the windows one by one."""
+        xs = []
+        for w in windows:
+            a = w.detach().to(torch.float32).numpy() if isinstance(w, torch.Tensor) else np.asarray(w, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != self.num_features:
+                raise ValueError(f"expected (T, {self.num_features}) windows, got {tuple(a.shape)}")
+            xs.append(a)
+        with torch.inference_mode():
+            if self.gru_size != 128:
+                return [self._predict(torch.from_numpy(np.ascontiguousarray(a))[None])[0] for a in xs]
+            eng = self.engine()
+            eng.drop_pending()                # (a batch started ahead into a promised buffer: waited for, then the promise is withdrawn)
+            eng.promise(None)
+            out = [None] * len(xs)
+            # a window whose tile of 8 alone exceeds the column budget of a pass (16 Mi: beyond 2 Mi columns) cannot be a ragged
+            # call; the rectangular entry takes it (as several passes are not needed for B = 1, it simply runs)
+            short = [i for i, a in enumerate(xs) if 8 * a.shape[0] <= _RAGGED_PASS_COLUMNS]
+            for i in set(range(len(xs))) - set(short):
+                out[i] = self._predict(torch.from_numpy(np.ascontiguousarray(xs[i]))[None])[0]
+            calls = [[short[k] for k in c] for c in
+                     _engine.ragged_calls([xs[i].shape[0] for i in short], half=self.half_precision, bidirectional=self.bidirectional,
+                                          gpu_share=gpu_share(), max_cols=max_cols)]
+            for idx in calls:
+                for i, p in zip(idx, eng.forward_ragged_host([xs[i] for i in idx])):
+                    out[i] = torch.from_numpy(p)
+            return out
 
     # -- opt-in fast paths around the network (SURVEY 8f rows f2, f3; no reference counterpart) ----
     def predict_on_counts(self, counts, depth, decoded=False):

@@ -48,6 +48,12 @@ def set_stage_target(engine):
     _stage_target = weakref.ref(engine) if engine is not None else None
 
 
+def stage_target():
+    """The engine batches are handed to at the moment, or None."""
+    ref = _stage_target
+    return ref() if ref is not None else None
+
+
 def forget_stage_target(engine):
     """`engine` is being closed: no further batch is handed to it."""
     global _stage_target
